@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the DCS-Net hot path on MI355X, one JSON line on rank 0.
 
-  python bench.py --gpus N --steps K --warmup W [--mode infer|train]
+  python bench.py --gpus N --steps K --warmup W [--mode infer|train] [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times K steps and prints the headline line.  --dump-outputs DIR then writes what the timed
+path computed in its last step as DIR/<name>.npy (float32; a fixed, seeded sample of an output above the size cap).
+--full adds everything the headline does not need (the roofline's instrumented pass, the CPU baseline, the native fp32 MFMA
+line and the other BASELINE configs' sub-lines); without it those fields are null.
 
 A "step" is one pass of the hot path over one synthetic batch already resident in HBM:
   infer  BASELINE.json configs[1]: C_NETWORK.eval() forward + bound/mask-apply/subtract,
@@ -11,7 +16,7 @@ A "step" is one pass of the hot path over one synthetic batch already resident i
 Utterances are independent, so ranks shard the batch with no data-path collective in `infer`
 (weak scaling: per-GPU work fixed) and one flat-bucket gradient all-reduce in `train`.
 
-Besides the contract fields the line carries
+With --full, besides the contract fields the line carries
   roofline      the dominant kernel (complex conv) timed live with HIP events inside the timed
                 region: algorithmic FLOPs of every launch / summed launch duration
   cpu_baseline  the CPU oracle (oracle/cnet_oracle.py, a port: the reference's Python never
@@ -333,6 +338,34 @@ def pmc_mfma_busy(mode, B, T):
     return None
 
 
+DUMP_BUDGET_BYTES = 48 << 20      # all --dump-outputs files together (the contract allows 64 MB)
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: {name: tensor} -> outdir/<name>.npy in float32 (complex as [..., 2] real / imaginary).  An output
+    larger than its share of DUMP_BUDGET_BYTES is written as a fixed sample of its flattened float32 elements: indices
+    drawn by a generator seeded from the name alone, in increasing order, so two builds sample the same elements.
+    Returns {name: (shape of the full output, number of values written)}."""
+    import zlib
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    info = {}
+    for name, t in arrays.items():
+        t = torch.full((1,), float('nan')) if t is None else t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t.contiguous())
+        t = t.float().cpu()
+        shape = list(t.shape)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randperm(t.numel(), generator=g)[:cap].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(outdir, f'{name}.npy'), t.numpy())
+        info[name] = (shape, t.numel())
+    return info
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -357,7 +390,17 @@ def main():
                          'v_mfma_f32_32x32x2_f32; bf16x6 = fp32 emulated on the bf16 MFMA (exact three-way bf16 splits of both '
                          'operands, six cross products, fp32 accumulate: error vs fp64 no larger than the native instruction\'s, '
                          'profiles/*conv_precision.txt)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one computed to DIR/<name>.npy (float32): train = the '
+                         'loss, the updated parameters and the gradients (the flat bucket); infer = the bounded mask and the '
+                         'noise / speech estimates; an output above its share of 48 MB as a fixed, seeded sample of its values')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the roofline (an instrumented pass after '
+                         'the timed region), the CPU baseline, the native fp32 MFMA line and the sub-lines of the other '
+                         'BASELINE configs (each still switched off by its --no-* flag)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     conv_mode = args.dtype if args.dtype != 'f32' else ('f32' if args.f32_mfma == 'native' else 'bf16x6')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -414,7 +457,7 @@ def main():
     # DCS_BENCH_TIMER_STRIDE=7 times every 7th launch only (a different residue each step): measured identical to timing
     # every launch (tools/micro/timer_stride_probe.py), i.e. the timers do not disturb their neighbours
     timer = ConvTimer(stride=int(os.environ.get('DCS_BENCH_TIMER_STRIDE', '1')))
-    ops.CONV_TIMER = timer
+    ops.CONV_TIMER = timer if args.full else None          # the roofline's launch accounting: --full only
 
     if train:
         from dcsnet.dp import TrainStep
@@ -476,28 +519,38 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     graphed = (train and ts.use_graph) or (not train and step is not eager_step)
-    timer.active = not graphed
+    timer.active = args.full and not graphed
     if timer.active:
         timer.stride = 1                  # un-graphed runs: every launch of the timed region carries a timer
     if train:
         ts.comm_events = []               # (start, end) events around every gradient all-reduce of the timed region
+    out = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         timer.next_step()
-        step()
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     timer.active = False
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: the instrumented pass of --full trains on
+        if train:
+            res = {'loss': out, 'params': ts.bucket.flat, 'grads': ts.bucket.grad}
+        else:
+            m_, n_, s_ = static_out if step is not eager_step else out
+            res = {'mask': m_, 'noise_estimate': n_, 'speech_estimate': s_}
+        for k_, (shape, n) in dump_outputs(args.dump_outputs, res).items():
+            log(f'dumped {k_}: {n} of the {shape} output\'s float32 values')
     comm_ms = None
     if train:
         ev, ts.comm_events = ts.comm_events, None
         if ev:
             d = sorted(a.elapsed_time(b) for a, b in ev)
             comm_ms = d[len(d) // 2]
-    if graphed and (rank == 0 or (train and world > 1)):
+    if args.full and graphed and (rank == 0 or (train and world > 1)):
         # kernels inside a hipGraph replay cannot be bracketed by events: time the conv family in an
         # instrumented EAGER pass of the same K steps, right after (and outside) the timed region.  Rank 0 holds the
         # timer; with world > 1 every rank runs the pass, because a train step contains the gradient all-reduce (a
@@ -541,19 +594,6 @@ def main():
     log(f'timed region done: {dt / args.steps * 1e3:.2f} ms/step')
     if rank == 0:
         frames = B * T * world * args.steps
-        cs = timer.summary()                                                               # per step
-        conv_ms, n_launch, conv_flops, conv_exec, conv_pipe_ms = cs['ms'], cs['n'], cs['flops'], cs['exec'], cs['pipe_ms']
-        # `peak` is the ceiling of the pipe the launches actually run on: launches that emulate an fp32
-        # product by six bf16 MFMAs are priced at bf16 peak / 6 = 416.7 TFLOP/s, native fp32-MFMA launches at 157.3, combined
-        # by the launches' flops (peak = flops / time-at-ceiling) — so `frac` cannot exceed 1 for work that is really done.
-        # `frac_vs_f32_mfma_peak` keeps the figure of rounds 1-2 (algorithmic fp32 flops over the fp32 MFMA peak), which is
-        # the "relevant per-GPU roofline" BASELINE.json's 70 % target was written against; it may exceed 1 for emulated launches.
-        if args.dtype != 'f32':
-            peak = PEAK_BF16_MFMA_TFLOPS
-        else:
-            peak = conv_flops / (cs['ceil_ms'] * 1e-3) / 1e12 if cs['ceil_ms'] > 0 else PEAK_F32_MFMA_TFLOPS
-        achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-        assert achieved <= peak * 1.0001, (achieved, peak)
         line = {
             'metric': ('STFT frames/sec (train fwd+bwd+Adam)' if train else
                        'STFT frames/sec (forward-only inference: C_NETWORK forward + bound/mask-apply/subtract)'),
@@ -588,125 +628,141 @@ def main():
                        'per_gpu_batch': B, 'frames_per_utterance': T, 'global_batch': B * world,
                        'frames_per_step': B * T * world, 'hip_graph': bool(graphed), 'parallelism': (f'dp{world} (utterance sharding, one flat-bucket gradient all-reduce)' if train
                                        else f'dp{world} (utterance sharding, no collective)')},
-            'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
-                         'frac': achieved / peak, 'traffic': pmc_traffic(args.mode, B, T),
-                         'peak_definition': ('flops-weighted ceiling of the pipes the launches run on: 2500 / 6 = 416.7 TFLOP/s for '
-                                             'launches that emulate fp32 on the bf16 MFMA (six MFMAs per product), 157.3 for native '
-                                             'fp32-MFMA launches' if args.dtype == 'f32' else 'dense bf16 MFMA peak'),
-                         'frac_vs_f32_mfma_peak': achieved / PEAK_F32_MFMA_TFLOPS,
-                         # what the same pipes SUSTAIN on this part (tools/micro/mfma_peak.hip, profiles/r03_mfma_peak_bf16.txt: a
-                         # bare bf16 MFMA loop runs at 1.845 GHz, 1.90 PFLOP/s -> 316 TFLOP/s of emulated fp32; fp32 MFMA 154.5)
-                         'sustained_peak': ({'bf16x6': SUSTAINED_BF16X6_TFLOPS, 'f32_mfma': SUSTAINED_F32_MFMA_TFLOPS,
-                                             'frac_of_flops_weighted': achieved / (conv_flops / (
-                                                 cs['emu_flops'] / SUSTAINED_BF16X6_TFLOPS +
-                                                 (conv_flops - cs['emu_flops']) / SUSTAINED_F32_MFMA_TFLOPS)) if conv_flops > 0 else None,
-                                             'source': 'profiles/r03_mfma_peak_bf16.txt'} if args.dtype == 'f32' else None),
-                         'emulated_share_of_flops': (cs['emu_flops'] / conv_flops if conv_flops > 0 else 0.0),
-                         'mfma_busy_pmc': pmc_mfma_busy(args.mode, B, T),
-                         'kernel': 'complex conv / convT (dcs_cconv2d_fwd' + (
-                             ', _bwd_data, _bwd_weight; the last decoder stage\'s backward dcs_cconv_up2_single_bwd_data / _bwd_weight '
-                             'counted with the flops of the 1x1 tap-conv launches it replaced in round 5' if train else '')
-                                   + '), all launches of the timed region',
-                         'launches_per_step': n_launch, 'kernel_ms_per_step': conv_ms,
-                         'samples_per_launch': timer.samples_per_launch(),
-                         'measured': ('HIP start / stop events attached to every kernel dispatch of the family '
-                                      '(hipExtLaunchKernelGGL through dcs_kernel_timer_*: the dispatch\'s own duration, as in '
-                                      'rocprofv3\'s kernel trace) in an instrumented pass of the same K steps right after the '
-                                      'timed region — the timed steps replay a hipGraph, whose nodes take no events; the '
-                                      'pass is enqueued behind a held stream and drains back to back; per launch the median over '
-                                      'the K steps.  The start stamp is a marker in front of the dispatch, so each launch '
-                                      'carries ~5 us of dispatch latency that the replayed graph does not pay: the committed '
-                                      'rocprofv3 kernel stats (profiles/) hold the dispatches\' own durations' if graphed else
-                                      'HIP start / stop events attached to every kernel dispatch of the family '
-                                      '(hipExtLaunchKernelGGL through dcs_kernel_timer_*) inside the timed region'),
-                         'algorithmic_gflop_per_step': conv_flops / 1e9,
-                         # MACs the kernels actually issue: the upsample-folded decoder launches run 6/9 or 4/9 of the
-                         # reference's taps (same result), so their algorithmic rate can exceed the MFMA peak; this one cannot
-                         'executed_gflop_per_step': conv_exec / 1e9,
-                         'executed_achieved': (conv_exec / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0),
-                         # share of the launches' time that the MFMA pipes need at their dense peak for the instructions
-                         # actually issued: executed fp32 flops at 157.3 TFLOP/s on the native path, six bf16 MFMA flops per
-                         # fp32 flop at 2500 TFLOP/s on the emulated one
-                         'executed_frac': (conv_pipe_ms / conv_ms if conv_ms > 0 else 0.0)},
         }
-        line['roofline']['algorithmic_gbytes_per_step'] = cs['bytes'] / 1e9
-        if bf16:
-            # BASELINE.md / SURVEY §8(d): with bf16 storage every conv stage sits below the bf16 ridge (310 flop/B) — the family's
-            # roofline is HBM.  achieved = algorithmic bytes (every activation read once and written once at 4 B per complex
-            # value, the weights once) / the launches' measured time; the MFMA figures stay beside it.
-            mf = dict(line['roofline'])
-            gbs = cs['bytes'] / (conv_ms * 1e-3) / 1e9 if conv_ms > 0 else 0.0
-            line['roofline'] = {'bound': 'hbm', 'achieved': gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': gbs / PEAK_HBM_GBS,
-                                'traffic': None, 'kernel': mf['kernel'], 'launches_per_step': n_launch,
-                                'kernel_ms_per_step': conv_ms, 'samples_per_launch': mf['samples_per_launch'],
-                                'algorithmic_gbytes_per_step': cs['bytes'] / 1e9, 'measured': mf['measured'],
-                                'mfma': {'achieved': mf['achieved'], 'peak': PEAK_BF16_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                                         'frac': mf['achieved'] / PEAK_BF16_MFMA_TFLOPS,
-                                         'algorithmic_gflop_per_step': mf['algorithmic_gflop_per_step']}}
-        # BASELINE.json's target names the ComplexConv2d ENCODER stack: its forward launches on their own (same pass)
-        es = timer.tag_summary('enc_fwd')
-        e_ms, e_n, e_fl = es['ms'], es['n'], es['flops']
-        if e_ms > 0:
-            e_tf = e_fl / (e_ms * 1e-3) / 1e12
-            e_peak = peak if args.dtype != 'f32' else e_fl / (es['ceil_ms'] * 1e-3) / 1e12
-            lp = lambda emu: PEAK_BF16_MFMA_TFLOPS if args.dtype != 'f32' else (PEAK_BF16X6_TFLOPS if emu else PEAK_F32_MFMA_TFLOPS)
-            line['roofline']['encoder_stack_forward'] = {
-                'achieved': e_tf, 'peak': e_peak, 'frac': e_tf / e_peak, 'frac_vs_f32_mfma_peak': e_tf / PEAK_F32_MFMA_TFLOPS,
-                'unit': 'TFLOP/s', 'launches_per_step': e_n, 'kernel_ms_per_step': e_ms,
-                'per_layer': [{'layer': f'enc{i}', 'us': ms * 1e3, 'tflops': fl / (ms * 1e-3) / 1e12,
-                               'pipe': 'bf16x6' if emu else ('f32' if args.dtype == 'f32' else 'bf16'),
-                               'frac': fl / (ms * 1e-3) / 1e12 / lp(emu),
-                               'frac_vs_f32_mfma_peak': fl / (ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS}
-                              for i, (ms, fl, emu) in enumerate(timer.tag_layers('enc_fwd'))]}
-        if not args.no_cpu_baseline and world == 1:
-            line['cpu_baseline'] = cpu_baseline_train(B, T) if train else cpu_baseline(B, T)
-        else:
-            line['cpu_baseline'] = None
-        line['native_f32_mfma'] = None
-        if world == 1 and args.dtype == 'f32' and conv_mode == 'bf16x6' and not args.no_native_line:
-            # the same timed region on the native fp32 MFMA, in a child process (its own graph, plans and packed panels)
-            import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), '--mode', args.mode, '--steps', str(args.steps), '--warmup',
-                   str(args.warmup), '--f32-mfma', 'native', '--no-cpu-baseline', '--no-native-line', '--no-sub-lines']
-            cmd += (['--batch', str(args.batch)] if args.batch else []) + (['--frames', str(args.frames)] if args.frames else [])
-            cmd += ['--no-graph'] if args.no_graph else []
-            try:
-                r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-                nat = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
-                enc = nat['roofline'].get('encoder_stack_forward') or {}
-                line['native_f32_mfma'] = {'value': nat['value'], 'ms_per_step': nat['ms_per_step'],
-                                           'roofline_frac': nat['roofline']['frac'],
-                                           'executed_frac': nat['roofline']['executed_frac'],
-                                           'encoder_stack_forward_frac': enc.get('frac'),
-                                           'kernel_ms_per_step': nat['roofline']['kernel_ms_per_step']}
-            except Exception as e:                              # the headline line must not depend on the second run
-                line['native_f32_mfma'] = {'error': repr(e)[:200]}
-        # The other single-GPU BASELINE configs, each measured by a fresh child process in this same run:
-        # configs[1] (forward-only inference, [16,256,2000]) and configs[4]'s per-GPU share (bf16 storage, B = 64 train step),
-        # each with its own roofline object — so that the driver's one `python bench.py --gpus 1` times all three.
-        line['sub_lines'] = None
-        if (world == 1 and train and args.dtype == 'f32' and conv_mode == 'bf16x6' and not args.no_sub_lines and not args.no_native_line and
-                args.batch is None and args.frames is None):
-            import subprocess
-            line['sub_lines'] = {}
-            common = ['--steps', str(args.steps), '--warmup', str(args.warmup), '--no-cpu-baseline', '--no-native-line',
-                      '--no-sub-lines'] + (['--no-graph'] if args.no_graph else [])
-            for name, extra in (('infer', ['--mode', 'infer']), ('bf16_b64', ['--mode', 'train', '--dtype', 'bf16', '--batch', '64'])):
+        if args.full:
+            cs = timer.summary()                                                               # per step
+            conv_ms, n_launch, conv_flops, conv_exec, conv_pipe_ms = cs['ms'], cs['n'], cs['flops'], cs['exec'], cs['pipe_ms']
+            # `peak` is the ceiling of the pipe the launches actually run on: launches that emulate an fp32
+            # product by six bf16 MFMAs are priced at bf16 peak / 6 = 416.7 TFLOP/s, native fp32-MFMA launches at 157.3, combined
+            # by the launches' flops (peak = flops / time-at-ceiling) — so `frac` cannot exceed 1 for work that is really done.
+            # `frac_vs_f32_mfma_peak` keeps the figure of rounds 1-2 (algorithmic fp32 flops over the fp32 MFMA peak), which is
+            # the "relevant per-GPU roofline" BASELINE.json's 70 % target was written against; it may exceed 1 for emulated launches.
+            if args.dtype != 'f32':
+                peak = PEAK_BF16_MFMA_TFLOPS
+            else:
+                peak = conv_flops / (cs['ceil_ms'] * 1e-3) / 1e12 if cs['ceil_ms'] > 0 else PEAK_F32_MFMA_TFLOPS
+            achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            assert achieved <= peak * 1.0001, (achieved, peak)
+            line['roofline'] = {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
+                                'frac': achieved / peak, 'traffic': pmc_traffic(args.mode, B, T),
+                                'peak_definition': ('flops-weighted ceiling of the pipes the launches run on: 2500 / 6 = 416.7 TFLOP/s for '
+                                                    'launches that emulate fp32 on the bf16 MFMA (six MFMAs per product), 157.3 for native '
+                                                    'fp32-MFMA launches' if args.dtype == 'f32' else 'dense bf16 MFMA peak'),
+                                'frac_vs_f32_mfma_peak': achieved / PEAK_F32_MFMA_TFLOPS,
+                                # what the same pipes SUSTAIN on this part (tools/micro/mfma_peak.hip, profiles/r03_mfma_peak_bf16.txt: a
+                                # bare bf16 MFMA loop runs at 1.845 GHz, 1.90 PFLOP/s -> 316 TFLOP/s of emulated fp32; fp32 MFMA 154.5)
+                                'sustained_peak': ({'bf16x6': SUSTAINED_BF16X6_TFLOPS, 'f32_mfma': SUSTAINED_F32_MFMA_TFLOPS,
+                                                    'frac_of_flops_weighted': achieved / (conv_flops / (
+                                                        cs['emu_flops'] / SUSTAINED_BF16X6_TFLOPS +
+                                                        (conv_flops - cs['emu_flops']) / SUSTAINED_F32_MFMA_TFLOPS)) if conv_flops > 0 else None,
+                                                    'source': 'profiles/r03_mfma_peak_bf16.txt'} if args.dtype == 'f32' else None),
+                                'emulated_share_of_flops': (cs['emu_flops'] / conv_flops if conv_flops > 0 else 0.0),
+                                'mfma_busy_pmc': pmc_mfma_busy(args.mode, B, T),
+                                'kernel': 'complex conv / convT (dcs_cconv2d_fwd' + (
+                                    ', _bwd_data, _bwd_weight; the last decoder stage\'s backward dcs_cconv_up2_single_bwd_data / _bwd_weight '
+                                    'counted with the flops of the 1x1 tap-conv launches it replaced in round 5' if train else '')
+                                          + '), all launches of the timed region',
+                                'launches_per_step': n_launch, 'kernel_ms_per_step': conv_ms,
+                                'samples_per_launch': timer.samples_per_launch(),
+                                'measured': ('HIP start / stop events attached to every kernel dispatch of the family '
+                                             '(hipExtLaunchKernelGGL through dcs_kernel_timer_*: the dispatch\'s own duration, as in '
+                                             'rocprofv3\'s kernel trace) in an instrumented pass of the same K steps right after the '
+                                             'timed region — the timed steps replay a hipGraph, whose nodes take no events; the '
+                                             'pass is enqueued behind a held stream and drains back to back; per launch the median over '
+                                             'the K steps.  The start stamp is a marker in front of the dispatch, so each launch '
+                                             'carries ~5 us of dispatch latency that the replayed graph does not pay: the committed '
+                                             'rocprofv3 kernel stats (profiles/) hold the dispatches\' own durations' if graphed else
+                                             'HIP start / stop events attached to every kernel dispatch of the family '
+                                             '(hipExtLaunchKernelGGL through dcs_kernel_timer_*) inside the timed region'),
+                                'algorithmic_gflop_per_step': conv_flops / 1e9,
+                                # MACs the kernels actually issue: the upsample-folded decoder launches run 6/9 or 4/9 of the
+                                # reference's taps (same result), so their algorithmic rate can exceed the MFMA peak; this one cannot
+                                'executed_gflop_per_step': conv_exec / 1e9,
+                                'executed_achieved': (conv_exec / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0),
+                                # share of the launches' time that the MFMA pipes need at their dense peak for the instructions
+                                # actually issued: executed fp32 flops at 157.3 TFLOP/s on the native path, six bf16 MFMA flops per
+                                # fp32 flop at 2500 TFLOP/s on the emulated one
+                                'executed_frac': (conv_pipe_ms / conv_ms if conv_ms > 0 else 0.0)}
+            line['roofline']['algorithmic_gbytes_per_step'] = cs['bytes'] / 1e9
+            if bf16:
+                # BASELINE.md / SURVEY §8(d): with bf16 storage every conv stage sits below the bf16 ridge (310 flop/B) — the family's
+                # roofline is HBM.  achieved = algorithmic bytes (every activation read once and written once at 4 B per complex
+                # value, the weights once) / the launches' measured time; the MFMA figures stay beside it.
+                mf = dict(line['roofline'])
+                gbs = cs['bytes'] / (conv_ms * 1e-3) / 1e9 if conv_ms > 0 else 0.0
+                line['roofline'] = {'bound': 'hbm', 'achieved': gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': gbs / PEAK_HBM_GBS,
+                                    'traffic': None, 'kernel': mf['kernel'], 'launches_per_step': n_launch,
+                                    'kernel_ms_per_step': conv_ms, 'samples_per_launch': mf['samples_per_launch'],
+                                    'algorithmic_gbytes_per_step': cs['bytes'] / 1e9, 'measured': mf['measured'],
+                                    'mfma': {'achieved': mf['achieved'], 'peak': PEAK_BF16_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                                             'frac': mf['achieved'] / PEAK_BF16_MFMA_TFLOPS,
+                                             'algorithmic_gflop_per_step': mf['algorithmic_gflop_per_step']}}
+            # BASELINE.json's target names the ComplexConv2d ENCODER stack: its forward launches on their own (same pass)
+            es = timer.tag_summary('enc_fwd')
+            e_ms, e_n, e_fl = es['ms'], es['n'], es['flops']
+            if e_ms > 0:
+                e_tf = e_fl / (e_ms * 1e-3) / 1e12
+                e_peak = peak if args.dtype != 'f32' else e_fl / (es['ceil_ms'] * 1e-3) / 1e12
+                lp = lambda emu: PEAK_BF16_MFMA_TFLOPS if args.dtype != 'f32' else (PEAK_BF16X6_TFLOPS if emu else PEAK_F32_MFMA_TFLOPS)
+                line['roofline']['encoder_stack_forward'] = {
+                    'achieved': e_tf, 'peak': e_peak, 'frac': e_tf / e_peak, 'frac_vs_f32_mfma_peak': e_tf / PEAK_F32_MFMA_TFLOPS,
+                    'unit': 'TFLOP/s', 'launches_per_step': e_n, 'kernel_ms_per_step': e_ms,
+                    'per_layer': [{'layer': f'enc{i}', 'us': ms * 1e3, 'tflops': fl / (ms * 1e-3) / 1e12,
+                                   'pipe': 'bf16x6' if emu else ('f32' if args.dtype == 'f32' else 'bf16'),
+                                   'frac': fl / (ms * 1e-3) / 1e12 / lp(emu),
+                                   'frac_vs_f32_mfma_peak': fl / (ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS}
+                                  for i, (ms, fl, emu) in enumerate(timer.tag_layers('enc_fwd'))]}
+            if not args.no_cpu_baseline and world == 1:
+                line['cpu_baseline'] = cpu_baseline_train(B, T) if train else cpu_baseline(B, T)
+            else:
+                line['cpu_baseline'] = None
+            line['native_f32_mfma'] = None
+            if world == 1 and args.dtype == 'f32' and conv_mode == 'bf16x6' and not args.no_native_line:
+                # the same timed region on the native fp32 MFMA, in a child process (its own graph, plans and packed panels)
+                import subprocess
+                cmd = [sys.executable, os.path.abspath(__file__), '--mode', args.mode, '--steps', str(args.steps), '--warmup',
+                       str(args.warmup), '--f32-mfma', 'native', '--full', '--no-cpu-baseline', '--no-native-line', '--no-sub-lines']
+                cmd += (['--batch', str(args.batch)] if args.batch else []) + (['--frames', str(args.frames)] if args.frames else [])
+                cmd += ['--no-graph'] if args.no_graph else []
                 try:
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra + common, capture_output=True,
-                                       text=True, timeout=600)
-                    sub = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
-                    rf = sub['roofline']
-                    keep = ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'kernel_ms_per_step', 'launches_per_step',
-                            'executed_frac', 'algorithmic_gflop_per_step', 'algorithmic_gbytes_per_step', 'mfma',
-                            'encoder_stack_forward')
-                    line['sub_lines'][name] = {'metric': sub['metric'], 'value': sub['value'], 'unit': sub['unit'],
-                                               'ms_per_step': sub['ms_per_step'], 'steps': sub['steps'], 'warmup': sub['warmup'],
-                                               'dtype': sub['dtype'].split(' ')[0], 'workload': sub['config']['workload'],
-                                               'hip_graph': sub['config']['hip_graph'],
-                                               'roofline': {k_: rf[k_] for k_ in keep if k_ in rf}}
-                except Exception as e:                          # the headline line must not depend on the extra runs
-                    line['sub_lines'][name] = {'error': repr(e)[:200]}
+                    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+                    nat = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+                    enc = nat['roofline'].get('encoder_stack_forward') or {}
+                    line['native_f32_mfma'] = {'value': nat['value'], 'ms_per_step': nat['ms_per_step'],
+                                               'roofline_frac': nat['roofline']['frac'],
+                                               'executed_frac': nat['roofline']['executed_frac'],
+                                               'encoder_stack_forward_frac': enc.get('frac'),
+                                               'kernel_ms_per_step': nat['roofline']['kernel_ms_per_step']}
+                except Exception as e:                              # the headline line must not depend on the second run
+                    line['native_f32_mfma'] = {'error': repr(e)[:200]}
+            # The other single-GPU BASELINE configs, each measured by a fresh child process in this same run:
+            # configs[1] (forward-only inference, [16,256,2000]) and configs[4]'s per-GPU share (bf16 storage, B = 64 train step),
+            # each with its own roofline object — so that one `python bench.py --gpus 1 --full` times all three.
+            line['sub_lines'] = None
+            if (world == 1 and train and args.dtype == 'f32' and conv_mode == 'bf16x6' and not args.no_sub_lines and not args.no_native_line and
+                    args.batch is None and args.frames is None):
+                import subprocess
+                line['sub_lines'] = {}
+                common = ['--steps', str(args.steps), '--warmup', str(args.warmup), '--full', '--no-cpu-baseline', '--no-native-line',
+                          '--no-sub-lines'] + (['--no-graph'] if args.no_graph else [])
+                for name, extra in (('infer', ['--mode', 'infer']), ('bf16_b64', ['--mode', 'train', '--dtype', 'bf16', '--batch', '64'])):
+                    try:
+                        r = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra + common, capture_output=True,
+                                           text=True, timeout=600)
+                        sub = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+                        rf = sub['roofline']
+                        keep = ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'kernel_ms_per_step', 'launches_per_step',
+                                'executed_frac', 'algorithmic_gflop_per_step', 'algorithmic_gbytes_per_step', 'mfma',
+                                'encoder_stack_forward')
+                        line['sub_lines'][name] = {'metric': sub['metric'], 'value': sub['value'], 'unit': sub['unit'],
+                                                   'ms_per_step': sub['ms_per_step'], 'steps': sub['steps'], 'warmup': sub['warmup'],
+                                                   'dtype': sub['dtype'].split(' ')[0], 'workload': sub['config']['workload'],
+                                                   'hip_graph': sub['config']['hip_graph'],
+                                                   'roofline': {k_: rf[k_] for k_ in keep if k_ in rf}}
+                    except Exception as e:                          # the headline line must not depend on the extra runs
+                        line['sub_lines'][name] = {'error': repr(e)[:200]}
+        else:
+            line.update(roofline=None, cpu_baseline=None, native_f32_mfma=None, sub_lines=None)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

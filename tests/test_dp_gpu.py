@@ -63,22 +63,38 @@ def test_two_rank_graph_replayed_train_step(tmp_path):
     assert all(l == l for l in r['losses'])
 
 
-@pytest.mark.parametrize('mode', ['train', 'infer'])
-def test_bench_two_rank_rehearsal(mode):
-    """bench.py launched exactly as the driver launches it for N = 2 (torch.distributed.run, one process per rank), with the
-    rehearsal switches that put both ranks on the one card and replace RCCL by gloo: the multi-rank control flow
-    (warm-up, barriers, graph A -> all-reduce -> graph B, the instrumented pass on every rank, MAX over ranks, one JSON
-    line from rank 0) must run to completion — a collective issued by one rank alone hangs the job."""
+def _two_rank_bench(mode, *flags):
+    """bench.py --gpus 2 at a small size under torch.distributed.run, both ranks on card 0 over gloo; rank 0's line."""
     import json
     import subprocess
     env = dict(os.environ, DCS_BENCH_DEVICE='0', DCS_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--mode', mode, '--steps', '2',
-           '--warmup', '1', '--no-cpu-baseline', '--batch', '4', '--frames', '64']
+           '--warmup', '1', *flags, '--batch', '4', '--frames', '64']
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, r.stdout[-500:]
     out = json.loads(lines[0])
     assert out['n_gpus'] == 2 and out['steps'] == 2 and out['value'] > 0 and out['scaling'] == 'weak'
-    assert out['config']['global_batch'] == 8 and out['roofline']['achieved'] > 0
+    assert out['config']['global_batch'] == 8 and out['config']['world_seen'] == 2
+    return out
+
+
+@pytest.mark.parametrize('mode', ['train', 'infer'])
+def test_bench_two_rank_rehearsal(mode):
+    """bench.py --full launched as a two-GPU run is launched (torch.distributed.run, one process per rank), with
+    the rehearsal switches that put both ranks on the one card and replace RCCL by gloo: the multi-rank control flow
+    (warm-up, barriers, graph A -> all-reduce -> graph B, the instrumented pass on every rank, MAX over ranks, one JSON
+    line from rank 0) must run to completion — a collective issued by one rank alone hangs the job."""
+    out = _two_rank_bench(mode, '--full', '--no-cpu-baseline')
+    assert out['roofline']['achieved'] > 0
+
+
+@pytest.mark.parametrize('mode', ['train', 'infer'])
+def test_bench_two_rank_rehearsal_plain(mode):
+    """The same without --full, the default: warm-up, barriers, the timed steps (graph A -> all-reduce -> graph B in train)
+    and the MAX over ranks, with no instrumented pass on any rank — and the --full figures null."""
+    out = _two_rank_bench(mode)
+    assert out['roofline'] is None and out['cpu_baseline'] is None
+    assert out['native_f32_mfma'] is None and out['sub_lines'] is None

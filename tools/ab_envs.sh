@@ -3,7 +3,7 @@
 #   tools/ab_envs.sh <tag> "<bench flags>" "<env A>" "<env B>" ...   (each env a string of assignments, may be empty)
 set -e -o pipefail
 R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/$1; mkdir -p $out; shift
-F="--no-cpu-baseline --no-native-line --no-sub-lines --steps 20 --warmup 5 $1"; shift
+F="--full --no-cpu-baseline --no-native-line --no-sub-lines --steps 20 --warmup 5 $1"; shift
 for rep in $(seq 1 ${REPS:-2}); do
   i=0
   for e in "$@"; do

@@ -2,7 +2,7 @@
 # diagnostic build:  python tools/exp_build.py knobs conv_mfma.hip -DDCS_PLAN_KNOBS ; export DCS_LIB_PATH=$PWD/dcs-net_amd/lib/exp/libdcsnet_hip_knobs.so
 # plan-threshold sweep for the bf16-storage train step at B = 64 (BASELINE configs[4] per-GPU share): one bench run per setting
 out=gpurun_out/$1; mkdir -p $out
-run() { name=$1; shift; env "$@" python bench.py --dtype bf16 --batch 64 --no-cpu-baseline --no-native-line --steps 20 > $out/$name.json 2>/dev/null; python -c "
+run() { name=$1; shift; env "$@" python bench.py --full --dtype bf16 --batch 64 --no-cpu-baseline --no-native-line --steps 20 > $out/$name.json 2>/dev/null; python -c "
 import json,sys
 j=json.loads(open('$out/$name.json').read().strip().splitlines()[-1]); print('$name', round(j['ms_per_step'],4), round(j['roofline']['kernel_ms_per_step'],3))"; }
 run base DCS_X=0

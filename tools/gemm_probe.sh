@@ -3,7 +3,7 @@
 set -e -o pipefail
 R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/$1; mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $R/bench.py --no-cpu-baseline --no-native-line --no-sub-lines --steps 10 --warmup 3 > $out/stats.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-native-line --no-sub-lines --steps 10 --warmup 3 > $out/stats.log 2>&1
 f=$(find $out/stats -name '*kernel_stats.csv' | head -1)
 python3 - "$f" <<'PY'
 import csv,sys

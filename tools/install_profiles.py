@@ -24,7 +24,7 @@ for mode, label in (('train', 'train B=32 T=256'), ('infer', 'infer B=16 T=2000'
     if os.path.exists(c):
         out = subprocess.run([sys.executable, os.path.join(REPO, 'tools', 'pmc_mfma_util.py'), c,
                               f'{label}: rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --kernel-trace -- python3 '
-                              f'bench.py --mode {mode} --no-graph --steps 2 --warmup 1 --no-cpu-baseline'],
+                              f'bench.py --full --mode {mode} --no-graph --steps 2 --warmup 1 --no-cpu-baseline'],
                              capture_output=True, text=True).stdout
         open(os.path.join(dst, f'{tag}_pmc_mfma_util_{mode}.txt'), 'w').write(out)
 commit = subprocess.run(['git', 'log', '-1', '--format=%s'], cwd=REPO, capture_output=True, text=True).stdout.strip()[:80]

@@ -2,7 +2,7 @@
 import json, sys, subprocess, os
 for st in (1, 7):
     env = dict(os.environ, DCS_BENCH_TIMER_STRIDE=str(st))
-    out = subprocess.run([sys.executable, 'bench.py', '--no-cpu-baseline'], env=env, capture_output=True, text=True)
+    out = subprocess.run([sys.executable, 'bench.py', '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])
     except Exception:

@@ -3,7 +3,7 @@
 set -e -o pipefail
 R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/$1; pat=$2; shift; shift
 mkdir -p $out; cd /tmp; export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $out/kt -- python3 $R/bench.py --no-cpu-baseline --no-native-line --no-sub-lines --steps 6 --warmup 3 "$@" > $out/kt.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $out/kt -- python3 $R/bench.py --full --no-cpu-baseline --no-native-line --no-sub-lines --steps 6 --warmup 3 "$@" > $out/kt.log 2>&1
 f=$(find $out/kt -name '*kernel_trace.csv' | head -1)
 python3 - "$f" "$pat" <<'PY'
 import csv,re,sys

@@ -46,7 +46,7 @@ for mode, label in (('train', 'train (B=32, T=256)'), ('infer', 'infer (B=16, T=
                  'config': ('B=32,T=256' if mode == 'train' else 'B=16,T=2000') + (f', commit "{commit}"' if commit else '')}
 out += ['', '# how: tools/collect_profiles.sh + tools/pmc_family_traffic.py — two separate passes per mode (TCC slots: FETCH_SIZE,',
         '# WRITE_SIZE), each with --kernel-trace only:',
-        '#   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 bench.py --mode <m> --no-graph --steps 2 --warmup 1 --no-cpu-baseline',
+        '#   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 bench.py --full --mode <m> --no-graph --steps 2 --warmup 1 --no-cpu-baseline',
         '#   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -- (same)',
         '# 3 steps per pass; KiB -> bytes x1024; FETCH_SIZE doubled (gfx950 counts 128-B requests as 64 B; MI355X_MICROARCH.md, HBM section).',
         '# calibration: adam must read 105 MB/step (36 B x 2.91 M parameters).',

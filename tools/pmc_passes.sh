@@ -15,7 +15,7 @@ G[tcc]="TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum"
 G[ta]="TA_BUSY_avr TA_TA_BUSY_sum TCP_GATE_EN1_sum TCP_GATE_EN2_sum"
 for g in ${GROUPS_ONLY:-wait inst mem tcp tcc ta}; do
   echo "[pmc] $g: ${G[$g]}"
-  if timeout -k 10 300 rocprofv3 --pmc ${G[$g]} --kernel-trace --output-format csv -d $out/p_$g -- python3 $R/bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline --no-native-line "$@" > $out/pmc_$g.log 2>&1; then
+  if timeout -k 10 300 rocprofv3 --pmc ${G[$g]} --kernel-trace --output-format csv -d $out/p_$g -- python3 $R/bench.py --full --no-graph --steps 2 --warmup 1 --no-cpu-baseline --no-native-line "$@" > $out/pmc_$g.log 2>&1; then
     cp $(find $out/p_$g -name "*counter_collection.csv" | head -1) $out/pmc_$g.csv
   else
     echo "[pmc] group $g failed (see pmc_$g.log)"; tail -5 $out/pmc_$g.log

@@ -51,7 +51,7 @@ for k, c in C.items():
         continue
     rows.append((DUR[k], k, c))
 rows.sort(key=lambda r: -r[0])
-print(f'# {d}: one eager train step pass per counter group (bench.py --no-graph --steps 2 --warmup 1), sums over all launches of a kernel')
+print(f'# {d}: one eager train step pass per counter group (bench.py --full --no-graph --steps 2 --warmup 1), sums over all launches of a kernel')
 print(f'{"us":>8s} {"n":>4s} {"mfma":>5s} {"wait":>5s} {"istall":>6s} {"ilds":>5s} {"active":>6s} {"valu/mf":>7s} {"lds/mf":>6s} {"vmem/mf":>7s} {"ldsbc":>5s} {"coex":>5s} {"tcp%":>5s} {"l2hit":>5s} {"tastl":>5s}  kernel')
 for dur, k, c in rows[:70]:
     mf = c.get('SQ_INSTS_MFMA', 0.0)
