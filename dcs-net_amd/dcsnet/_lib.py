@@ -148,6 +148,9 @@ SIGNATURES = {
     'dcs_pack_plan_jobs': (_I, [_P, _P, _P]),
     'dcs_pack_plan_run': (_I, [_P, _P]),
     'dcs_pack_plan_destroy': (_I, [_P]),
+    'dcs_resample_poly_f32': (_I, [_P, _P, _I, _L, _P, _I, _I, _I, _P]),
+    'dcs_stoi_workspace_bytes': (_L, [_I, _L]),
+    'dcs_stoi_f32': (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _P, _L, _P]),
 }
 
 _lib = None

@@ -33,6 +33,8 @@ class Config(object):
             # run control
             tune=False, max_epochs=200, num_gpus=gpus, num_loader_workers=4 * gpus, precision=32, seed=0,
             detect_anomaly=True, val_log_sample_size=1,
+            # STOI of the validation / test steps on the device (metrics.stoi_batch) instead of the host loop; off by default
+            stoi_on_device=False,
             # audio / STFT front end
             sr=sr, file_sr=48000, fft_size=n_fft, window_length=n_fft, hop_length=hop,
             window=torch.hann_window(window_length=n_fft), normalise_audio=True, normalise_stft=True,

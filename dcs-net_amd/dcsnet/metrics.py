@@ -13,6 +13,12 @@ numpy, as in the reference (which calls `.cpu().numpy()` per utterance), and is 
 imported.  PARITY UNPINNED: there is no pystoi here to compare with and the reference holds no STOI vectors; the
 tests check the algorithm's defining properties only (tests/test_host_cpu.py).
 
+STOI on the device.  `stoi_batch()` restates `stoi()` below for a whole batch of device tensors [B, L] (csrc/stoi.hip,
+through ops.resample_poly and ops.stoi): the same resampler (its closed polyphase form with the same normalised window), the
+same framing, silent-frame test, window, band edges, clipping and segment statistics, with the frame energies and the keep
+test in fp64.  `stoi()` is its numerics contract (tests/test_stoi_device.py); parity with pystoi itself stays unpinned.
+`network_functions.calc_metric` uses it when `config.stoi_on_device` is set (default off: the host loop).
+
 PESQ.  ITU-T P.862 is ~2 k lines of reference C with psychoacoustic tables; it is not restated.  `pesq` stays the
 imported package when present, else None (calc_metric then reports NaN, as in round 1)."""
 import numpy as np
@@ -129,3 +135,62 @@ def stoi(x, y, fs_sig, extended=False):
     yp = yp / (np.linalg.norm(yp, axis=2, keepdims=True) + EPS)
     xz = xz / (np.linalg.norm(xz, axis=2, keepdims=True) + EPS)
     return float(np.sum(yp * xz) / (xseg.shape[0] * xseg.shape[1]))
+
+
+# ---- the device path -------------------------------------------------------------------------------------------------
+
+_device_tables = {}
+
+
+def stoi_band_edges(device):
+    """thirdoct(10000, 512, 15, 150)'s rows as bin ranges [lo, hi): int32 [2, 15] on `device` (cached)."""
+    key = ('bands', str(device))
+    t = _device_tables.get(key)
+    if t is None:
+        import torch
+        obm, _ = thirdoct(FS, NFFT, NUMBAND, MINFREQ)
+        lo, hi = [], []
+        for row in obm:
+            nz = np.flatnonzero(row)
+            a = int(nz[0]) if len(nz) else 0
+            b = int(nz[-1]) + 1 if len(nz) else 0
+            assert len(nz) == b - a, 'thirdoct rows are contiguous bin ranges'
+            lo.append(a)
+            hi.append(b)
+        t = torch.tensor([lo, hi], dtype=torch.int32).to(device)
+        _device_tables[key] = t
+    return t
+
+
+def resample_taps(fs_sig, device):
+    """(h float32 [taps] on `device` = the normalised window of resample_oct(., FS, fs_sig), up, down) (cached)."""
+    fs_sig = int(fs_sig)
+    key = ('taps', fs_sig, str(device))
+    t = _device_tables.get(key)
+    if t is None:
+        import torch
+        g = int(np.gcd(FS, fs_sig))
+        h = _resample_window_oct(FS, fs_sig)
+        t = (torch.tensor(h / np.sum(h), dtype=torch.float32).to(device), FS // g, fs_sig // g)
+        _device_tables[key] = t
+    return t
+
+
+def stoi_batch(clean, estimate, fs_sig):
+    """stoi(clean[i], estimate[i], fs_sig) for every row of two device tensors [B, L] of equal shape: a float32 [B] device
+    tensor, computed by the HIP kernels of csrc/stoi.hip without a host read-back (capturable).  CPU tensors raise
+    DcsHipError: there is no host fallback here (stoi() is the host function)."""
+    from . import ops
+    from ._lib import DcsHipError
+    import torch
+    if not (isinstance(clean, torch.Tensor) and isinstance(estimate, torch.Tensor) and clean.is_cuda and estimate.is_cuda):
+        raise DcsHipError('stoi_batch: expected CUDA (HIP) tensors; the device path has no CPU fallback (use stoi())')
+    if clean.shape != estimate.shape or clean.dim() != 2:
+        raise ValueError(f'stoi_batch: clean {tuple(clean.shape)} and estimate {tuple(estimate.shape)} must be [B, L] of equal shape')
+    clean = clean.to(torch.float32).contiguous()
+    estimate = estimate.to(torch.float32).contiguous()
+    bands = stoi_band_edges(clean.device)
+    if int(fs_sig) != FS:
+        h, up, down = resample_taps(fs_sig, clean.device)
+        clean, estimate = ops.resample_poly(clean, h, up, down), ops.resample_poly(estimate, h, up, down)
+    return ops.stoi(clean, estimate, bands)[0]

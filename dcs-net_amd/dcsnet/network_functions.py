@@ -14,6 +14,7 @@ import sys
 import torch
 
 from . import functional as F
+from . import metrics as _metrics
 from . import ops
 
 try:                                     # metric packages are absent from this image
@@ -224,6 +225,10 @@ def _polar_wave(z, eps, config):
 def calc_metric(clean_audio, predict_audio, config, metric):
     if metric is None:
         return float('nan')
+    if getattr(config, 'stoi_on_device', False) and (metric is stoi or metric is _metrics.stoi):
+        # the whole batch in HIP kernels (metrics.stoi_batch restates metrics.stoi); one read-back per batch
+        vals = [v for v in _metrics.stoi_batch(clean_audio, predict_audio, config.sr).tolist() if v == v]
+        return float(sum(vals)) / max(len(vals), 1)
     vals = []
     for i in range(predict_audio.shape[0]):
         v = metric(clean_audio[i, :].cpu().numpy(), predict_audio[i, :].cpu().numpy(), config.sr)

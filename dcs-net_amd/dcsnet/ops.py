@@ -1276,6 +1276,56 @@ def crm(S, Y, eps=1e-8):
     return M
 
 
+# ---- STOI (dcsnet/metrics.py::stoi on the device, csrc/stoi.hip) ----------------------------------------------------
+
+def resample_poly(x, h, up, down):
+    """Octave-style polyphase resampling (metrics.resample_oct) of the rows of float [..., L] by up / down with the
+    normalised window h float [taps] (taps odd; dcs_resample_poly_f32) -> [..., ceil(L up / down)]."""
+    _chk(x, 'x')
+    _chk(h, 'h', 1)
+    if x.dim() < 1:
+        raise _lib.DcsHipError('resample_poly: x needs a last (time) dimension')
+    L = x.shape[-1]
+    up, down = int(up), int(down)
+    if up <= 0 or down <= 0:
+        raise _lib.DcsHipError(f'resample_poly: up={up}, down={down}')
+    y = torch.empty((*x.shape[:-1], -(-L * up // down)), dtype=torch.float32, device=x.device)
+    if y.numel():
+        check(_lib.load().dcs_resample_poly_f32(ptr(x), ptr(y), x.numel() // L, L, ptr(h), h.numel(), up, down, cur_stream()),
+              'dcs_resample_poly_f32')
+    return y
+
+
+def stoi(clean10, est10, bands=None):
+    """STOI of B utterances of equal length at 10 kHz: float [B, L10] each -> (d float [B], kept int32 [B] frames kept by the
+    silent-frame removal) (dcs_stoi_f32).  bands: int32 [2, 15] one-third-octave bin ranges [lo, hi) on the same device
+    (default: metrics.stoi_band_edges)."""
+    _chk(clean10, 'clean10', 2)
+    _chk(est10, 'est10', 2)
+    if clean10.shape != est10.shape:
+        raise _lib.DcsHipError(f'stoi: clean {tuple(clean10.shape)} vs estimate {tuple(est10.shape)}')
+    dev = clean10.device
+    if bands is None:
+        from .metrics import stoi_band_edges
+        bands = stoi_band_edges(dev)
+    if bands.dtype != torch.int32 or tuple(bands.shape) != (2, 15) or not bands.is_contiguous() or bands.device != dev:
+        raise _lib.DcsHipError(f'stoi: bands must be a contiguous int32 [2, 15] tensor on {dev}')
+    B, L = clean10.shape
+    d = torch.empty(B, dtype=torch.float32, device=dev)
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return d, kept
+    lib = _lib.load()
+    nbytes = lib.dcs_stoi_workspace_bytes(B, L)
+    if nbytes < 0:
+        raise _lib.DcsHipError(f'stoi: unsupported shape [{B}, {L}]')
+    ws = _workspace(nbytes, dev)
+    sig = (ptr(clean10), ptr(est10)) if L else (None, None)
+    check(lib.dcs_stoi_f32(*sig, B, L, ptr(bands[0]), ptr(bands[1]), ptr(d), ptr(kept), ptr(ws), ws.numel(), cur_stream()),
+          'dcs_stoi_f32')
+    return d, kept
+
+
 # ---- complex <-> channels-last float views -------------------------------------------------
 
 def to_nhwc(z):

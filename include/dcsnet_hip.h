@@ -810,6 +810,24 @@ int dcs_pack_plan_jobs(const void* plan, int* n_jobs, int* n_launches);
 int dcs_pack_plan_run(const void* plan, dcs_stream_t stream);
 int dcs_pack_plan_destroy(void* plan);
 
+/* ------------------------------------------------------------------------------------
+ * STOI of a whole validation / test batch (network_functions.py:152-166 scores each utterance on the host with
+ * pystoi.stoi; here dcsnet/metrics.py::stoi, its in-tree restatement, is the numerics contract), stoi.hip.
+ * dcs_resample_poly_f32: the Octave-style polyphase resampler of metrics.resample_oct, x float[rows][L] ->
+ *   y float[rows][ceil(L up / down)], y[n] = up * sum_k h[k] x[(n down + (taps - 1) / 2 - k) / up] over the k that make the
+ *   index an integer inside [0, L); h float[taps] (taps odd) = the normalised window h / sum(h).  rows <= 65535, L > 0.
+ * dcs_stoi_workspace_bytes: pure host arithmetic, the workspace of dcs_stoi_f32 for (B, L10); < 0 for bad arguments.
+ * dcs_stoi_f32: out_d float[b] = stoi(clean10[b], est10[b], 10000) and out_kept int[b] = the number of frames the silent-frame
+ *   removal keeps, for B utterances of L10 >= 0 samples at 10 kHz (float[B][L10] each; may be null when L10 = 0).
+ *   band_lo / band_hi int[15]: the one-third-octave bands as bin ranges [lo, hi) (metrics.thirdoct(10000, 512, 15, 150)).
+ *   Frame energies and the keep test in fp64, spectra in fp32, segment statistics in fp64; exactly 1e-5 when fewer than 30
+ *   STFT frames remain.  Three launches sized from (B, L10) alone, fixed reduction orders (bit-reproducible), no sync. */
+int dcs_resample_poly_f32(const float* x, float* y, int rows, long L, const float* h, int taps, int up, int down,
+                          dcs_stream_t stream);
+long dcs_stoi_workspace_bytes(int B, long L10);
+int dcs_stoi_f32(const float* clean10, const float* est10, int B, long L10, const int* band_lo, const int* band_hi,
+                 float* out_d, int* out_kept, void* workspace, long workspace_bytes, dcs_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * bf16 activation storage (BASELINE.json configs[4]: bf16 activations in HBM, fp32 accumulation / statistics / parameters /
  * optimizer; the reference itself trains at precision 32: config.py:70, train.py:144 — this is the build's stated
