@@ -5,7 +5,8 @@ bins 1..n_fft/2), for a whole batch of waveforms already on the GPU.
     frames (HIP: window + reflect padding, all three signals)  ->  one batched contiguous real FFT (fft512.hip at n_fft = 512, else rocFFT via torch.fft)
     ->  bins (HIP: drop the DC bin, 1/sqrt(n_fft), transpose to the network's [B, 256, T] layout)
 
-Resampling (data.py:84-85, torchaudio) and file decoding stay with the loader; they are out of scope."""
+Resampling (data.py:84-85, torchaudio) and WAV decoding for a training set held in HBM are in audio_store.py, whose batch
+op is the crop and this front end fused into one launch, bit for bit the same result."""
 import torch
 
 from . import ops

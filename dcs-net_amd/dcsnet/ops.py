@@ -1326,6 +1326,159 @@ def stoi(clean10, est10, bands=None):
     return d, kept
 
 
+# ---- HBM-resident training audio (csrc/audio_store.hip, dcsnet/audio_store.py) ----------------------------------------
+
+_SINC_LOWPASS_WIDTH, _SINC_ROLLOFF = 6, 0.99                 # torchaudio 0.9.0's Resample defaults (config.py:61)
+_sinc_taps = {}
+
+
+def sinc_resample_geometry(orig, new):
+    """(o, n, width, K) of torchaudio 0.9.0's sinc resampler from orig to new Hz: the gcd-reduced rates, the half width and
+    the taps per phase (48 kHz -> 16 kHz: (3, 1, 19, 41))."""
+    import math
+    orig, new = int(orig), int(new)
+    if orig <= 0 or new <= 0:
+        raise _lib.DcsHipError(f'resample_sinc: rates must be positive, got {orig} -> {new}')
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    base = min(o, n) * _SINC_ROLLOFF
+    width = math.ceil(_SINC_LOWPASS_WIDTH * o / base)
+    return o, n, width, 2 * width + o
+
+
+def sinc_resample_taps(orig, new):
+    """torchaudio 0.9.0's _get_sinc_resample_kernel in float64, in its order of operations: float64 [n, K], phase i in row i.
+    Resample rounds it once to float32."""
+    import numpy as np
+    o, n, width, K = sinc_resample_geometry(orig, new)
+    base = min(o, n) * _SINC_ROLLOFF
+    idx = np.arange(-width, width + o, dtype=np.float64)
+    t = (-np.arange(n, dtype=np.float64)[:, None] / n + idx[None, :] / o) * base
+    t = np.clip(t, -_SINC_LOWPASS_WIDTH, _SINC_LOWPASS_WIDTH)
+    window = np.cos(t * np.pi / _SINC_LOWPASS_WIDTH / 2) ** 2
+    t = t * np.pi
+    with np.errstate(divide='ignore', invalid='ignore'):
+        h = np.where(t == 0, 1.0, np.sin(t) / t)
+    return h * window * (base / o)
+
+
+def resample_sinc_length(L, orig, new):
+    """Output length of Resample(orig, new) for L input samples: ceil(n L / o) (L at equal rates)."""
+    if int(orig) == int(new):
+        return int(L)
+    o, n, _, _ = sinc_resample_geometry(orig, new)
+    return -(-n * int(L) // o)
+
+
+def _sinc_taps_on(orig, new, device):
+    key = (int(orig), int(new), device)
+    t = _sinc_taps.get(key)
+    if t is None:
+        t = torch.from_numpy(sinc_resample_taps(orig, new).astype('float32')).to(device)
+        _sinc_taps[key] = t
+    return t
+
+
+def resample_sinc(x, orig, new, offsets=None, out=None):
+    """torchaudio.transforms.Resample(orig, new) with torchaudio 0.9.0's defaults on the device (dcs_resample_sinc_f32).
+    x float32: rows of one length [..., L] -> [..., ceil(n L / o)]; or, with offsets (int64 [rows + 1] prefix offsets on the
+    host, offsets[-1] = x.numel()), the 1-D concatenation of ragged rows -> the 1-D concatenation of their outputs, row r at
+    the prefix sums of resample_sinc_length.  All rows in one launch.  Equal rates return x itself, as Resample.forward does.
+    out: the destination (a contiguous float32 tensor of the result's shape)."""
+    _chk(x, 'x')
+    _chk(out, 'out')
+    if offsets is None:
+        if x.dim() < 1:
+            raise _lib.DcsHipError('resample_sinc: x needs a last (time) dimension')
+        L = x.shape[-1]
+        rows = x.numel() // L if L else 0
+        x_off = torch.arange(rows + 1, dtype=torch.int64) * L
+        shape = (*x.shape[:-1], resample_sinc_length(L, orig, new))
+    else:
+        if x.dim() != 1:
+            raise _lib.DcsHipError(f'resample_sinc: ragged rows need a 1-D x, got shape {tuple(x.shape)}')
+        x_off = torch.as_tensor(offsets, dtype=torch.int64).cpu().reshape(-1)
+        if (x_off.numel() < 2 or int(x_off[0]) != 0 or int(x_off[-1]) != x.numel() or bool((x_off[1:] < x_off[:-1]).any())):
+            raise _lib.DcsHipError(f'resample_sinc: offsets must rise from 0 to x.numel() = {x.numel()}')
+        rows = x_off.numel() - 1
+        shape = None
+    sinc_resample_geometry(orig, new)                         # (validates the rates)
+    if int(orig) == int(new):
+        if out is None:
+            return x
+        if out.shape != x.shape:
+            raise _lib.DcsHipError(f'resample_sinc: out {tuple(out.shape)} for {tuple(x.shape)}')
+        return out.copy_(x)
+    o, n, width, _ = sinc_resample_geometry(orig, new)
+    y_off = torch.zeros_like(x_off)
+    torch.cumsum(-(-n * (x_off[1:] - x_off[:-1]) // o), 0, out=y_off[1:])
+    total = int(y_off[-1])
+    if shape is None:
+        shape = (total,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != tuple(shape) or out.device != x.device:
+        raise _lib.DcsHipError(f'resample_sinc: out {tuple(out.shape)} on {out.device}, expected {tuple(shape)} on {x.device}')
+    if total:
+        offs = torch.stack([x_off, y_off]).to(x.device)      # one upload; stream-ordered lifetime
+        check(_lib.load().dcs_resample_sinc_f32(ptr(x), ptr(offs[0]), ptr(out), ptr(offs[1]), rows, total,
+                                                ptr(_sinc_taps_on(orig, new, x.device)), o, n, width, cur_stream()),
+              'dcs_resample_sinc_f32')
+    return out
+
+
+def _chk_index(t, name, dtype, B=None):
+    if not t.is_cuda:
+        raise _lib.DcsHipError(f'{name}: expected a CUDA (HIP) tensor; the HIP path has no CPU fallback')
+    if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or (B is not None and t.numel() != B):
+        raise _lib.DcsHipError(f'{name}: expected a contiguous 1-D {dtype} tensor{"" if B is None else f" of {B}"}, '
+                               f'got {t.dtype} {tuple(t.shape)}')
+
+
+def audio_stft_batch(clean, noisy, offsets, index, starts, window, T, hop, scale, out=None):
+    """One training batch from a resident store in one launch (dcs_audio_stft_batch_f32).  clean / noisy float32 [N]: the
+    utterances concatenated, utterance u at [offsets[u], offsets[u + 1]) (offsets int64 [n_items + 1] on the device, non-decreasing,
+    offsets[-1] <= N: the caller's invariant, as DeviceAudioStore builds them); index / starts
+    int32 [B] (device): item b is the crop [starts[b], starts[b] + hop (T - 1)) of utterance index[b], zero past its end.
+    -> (noise, noisy, clean) complex64 [B, 256, T]: bit for bit frontend.stft_batch of the crops (n_fft = 512 only).  An
+    out-of-range index or start gives zeros for that item.  out: three contiguous complex64 [B, 256, T] tensors to write
+    (e.g. TrainStep.input_buffers())."""
+    _chk(clean, 'clean', 1)
+    _chk(noisy, 'noisy', 1)
+    _chk(window, 'window', 1)
+    _chk_index(offsets, 'offsets', torch.int64)
+    _chk_index(index, 'index', torch.int32)
+    B = index.numel()
+    _chk_index(starts, 'starts', torch.int32, B)
+    if window.numel() != 512:
+        raise _lib.DcsHipError(f'audio_stft_batch: n_fft = 512 only, got a window of {window.numel()}')
+    if clean.shape != noisy.shape or offsets.numel() < 2:
+        raise _lib.DcsHipError(f'audio_stft_batch: clean {tuple(clean.shape)}, noisy {tuple(noisy.shape)}, '
+                               f'{offsets.numel()} offsets')
+    T, hop = int(T), int(hop)
+    if B == 0 or B > 65535 or T < 2 or hop <= 0 or hop * (T - 1) <= 256:
+        raise _lib.DcsHipError(f'audio_stft_batch: B={B}, T={T}, hop={hop} (need 1 <= B <= 65535, hop (T - 1) > 256)')
+    dev = clean.device
+    if out is None:
+        out = tuple(torch.empty((B, 256, T), dtype=torch.complex64, device=dev) for _ in range(3))
+    else:
+        out = tuple(out)
+        if len(out) != 3:
+            raise _lib.DcsHipError(f'audio_stft_batch: out must hold (noise, noisy, clean), got {len(out)} tensors')
+        for name, t in zip(('noise', 'noisy', 'clean'), out):
+            if (t.dtype != torch.complex64 or tuple(t.shape) != (B, 256, T) or not t.is_contiguous() or
+                    t.device != dev):
+                raise _lib.DcsHipError(f'audio_stft_batch: out[{name}] must be a contiguous complex64 [{B}, 256, {T}] on {dev}')
+    for t in (noisy, offsets, index, starts, window):
+        if t.device != dev:
+            raise _lib.DcsHipError(f'audio_stft_batch: every tensor on {dev}')
+    noise_o, noisy_o, clean_o = out
+    check(_lib.load().dcs_audio_stft_batch_f32(ptr(clean), ptr(noisy), ptr(offsets), offsets.numel() - 1, ptr(index), ptr(starts),
+                                               B, ptr(window), 512, T, hop, float(scale), ptr(noise_o), ptr(noisy_o),
+                                               ptr(clean_o), cur_stream()), 'dcs_audio_stft_batch_f32')
+    return out
+
+
 # ---- complex <-> channels-last float views -------------------------------------------------
 
 def to_nhwc(z):

@@ -828,6 +828,30 @@ long dcs_stoi_workspace_bytes(int B, long L10);
 int dcs_stoi_f32(const float* clean10, const float* est10, int B, long L10, const int* band_lo, const int* band_hi,
                  float* out_d, int* out_kept, void* workspace, long workspace_bytes, dcs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * HBM-resident training audio (data.py:68-143: resample, crop, noise = noisy - clean, three torch.stft calls per item on the
+ * loader workers; dcsnet/audio_store.py), audio_store.hip.
+ * dcs_resample_sinc_f32: torchaudio.transforms.Resample(orig * g, new_ * g) of torchaudio 0.9.0 (sinc_interpolation, lowpass
+ *   filter width 6, rolloff 0.99) over ragged rows in one launch.  orig / new_ are the gcd-reduced rates o / n, width =
+ *   ceil(6 o / (0.99 min(o, n))), taps float[n][2 width + o] the fp64-computed, once-rounded filter bank of
+ *   _get_sinc_resample_kernel (row i = phase i).  Row r is x[x_off[r] .. x_off[r + 1]) and its output
+ *   y[y_off[r] .. y_off[r + 1]), y_off[r + 1] - y_off[r] = ceil(n (x_off[r + 1] - x_off[r]) / o):
+ *   y[y_off[r] + j n + i] = sum_k taps[i][k] x_r[j o + k - width] (k ascending, fp32; x_r = 0 outside the row).  x_off / y_off:
+ *   int64[rows + 1] non-decreasing prefix offsets on the device, total_out = y_off[rows].  Equal rates are the caller's (the
+ *   input is its own resampling).
+ * dcs_audio_stft_batch_f32: one training batch from a resident store in one launch.  clean / noisy float[offsets[n_items]]:
+ *   utterance u is [offsets[u], offsets[u + 1]) of each (int64 offsets on the device).  item_index / item_start int[B] on the
+ *   device: item b is the crop [item_start[b], item_start[b] + L) of utterance item_index[b], L = hop (T - 1), zero past the
+ *   utterance's end.  out_noise / out_noisy / out_clean complex[B][256][T] = frontend.stft_batch of those crops, bit for bit
+ *   (reflect-padded frames with window float[512], noise = noisy - clean in the time domain, the 512-point real FFT, bins
+ *   1 .. 256, times scale, [B][F][T]).  An index outside [0, n_items), a negative start or a non-zero start with start + L past the
+ *   utterance's end gives zeros for that item: nothing outside the store is read.  n_fft = 512 only, L > 256.  No sync. */
+int dcs_resample_sinc_f32(const float* x, const long* x_off, float* y, const long* y_off, int rows, long total_out,
+                          const float* taps, int orig, int new_, int width, dcs_stream_t stream);
+int dcs_audio_stft_batch_f32(const float* clean, const float* noisy, const long* offsets, int n_items, const int* item_index,
+                             const int* item_start, int B, const float* window, int n_fft, int T, int hop, float scale,
+                             float* out_noise, float* out_noisy, float* out_clean, dcs_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * bf16 activation storage (BASELINE.json configs[4]: bf16 activations in HBM, fp32 accumulation / statistics / parameters /
  * optimizer; the reference itself trains at precision 32: config.py:70, train.py:144 — this is the build's stated
