@@ -6,6 +6,7 @@
 //     g = scale * g ;  g *= min(1, max_norm / (||g|| + 1e-6)) ;  g += wd * p
 //     m = b1 m + (1-b1) g ;  v = b2 v + (1-b2) g^2 ;  vmax = max(vmax, v)
 //     p -= lr / (1-b1^t) * m / (sqrt(vmax) / sqrt(1-b2^t) + eps)
+// lr is a DEVICE scalar (ABI 19): a learning-rate schedule written between replays reaches a captured step.
 // HBM-bound: 5 streams read, 4 written = 36 B per parameter; the global norm comes from the caller
 // as a DEVICE scalar (no host synchronisation in the step).
 #include "dcs_common.h"
@@ -17,7 +18,8 @@ __global__ __launch_bounds__(kThreads) void adam_amsgrad_kernel(float4* __restri
                                                                  float4* __restrict__ m, float4* __restrict__ v,
                                                                  float4* __restrict__ vmax,
                                                                  const float* __restrict__ grad_norm, float max_norm,
-                                                                 float grad_scale, long n4, long n, float lr, float b1,
+                                                                 float grad_scale, long n4, long n,
+                                                                 const float* __restrict__ lr, float b1,
                                                                  float b2, float eps, float wd, float bc1, float bc2s,
                                                                  const int* __restrict__ step_dev,
                                                                  const float* __restrict__ skip,
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(kThreads) void adam_amsgrad_kernel(float4* __restri
         const float c = max_norm / (grad_scale * (n_parts > 0 ? norm_parts : grad_norm[0]) + 1e-6f);
         clip *= c < 1.f ? c : 1.f;
     }
-    const float step = lr / bc1;
+    const float step = lr[0] / bc1;
     auto upd = [&](float& pp, float gg, float& mm, float& vv, float& vm) {
         gg = fmaf(wd, pp, gg * clip);
         mm = fmaf(b1, mm, (1.f - b1) * gg);
@@ -78,9 +80,9 @@ __global__ __launch_bounds__(kThreads) void adam_amsgrad_kernel(float4* __restri
 }  // namespace
 
 static int adam_launch(float* p, const float* g, float* m, float* v, float* vmax, const float* grad_norm, const double* sumsq_parts,
-                       int n_parts, float max_norm, float grad_scale, long n, float lr, float beta1, float beta2, float eps,
+                       int n_parts, float max_norm, float grad_scale, long n, const float* lr, float beta1, float beta2, float eps,
                        float weight_decay, int step, const int* step_dev, const float* skip, dcs_stream_t stream) {
-    if (!p || !g || !m || !v || !vmax || n <= 0 || (step < 1 && !step_dev)) return DCS_ERR_BADARG;
+    if (!p || !g || !m || !v || !vmax || !lr || n <= 0 || (step < 1 && !step_dev)) return DCS_ERR_BADARG;
     if (n_parts < 0 || n_parts > 1024 || (n_parts > 0 && !sumsq_parts)) return DCS_ERR_BADARG;
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)vmax) & 15) return DCS_ERR_BADARG;
     const float bc1 = 1.f - powf(beta1, (float)(step < 1 ? 1 : step));
@@ -96,7 +98,7 @@ static int adam_launch(float* p, const float* g, float* m, float* v, float* vmax
 }
 
 extern "C" int dcs_adam_amsgrad_step(float* p, const float* g, float* m, float* v, float* vmax, const float* grad_norm,
-                                     float max_norm, float grad_scale, long n, float lr, float beta1, float beta2,
+                                     float max_norm, float grad_scale, long n, const float* lr, float beta1, float beta2,
                                      float eps, float weight_decay, int step, const int* step_dev, const float* skip,
                                      dcs_stream_t stream) {
     return adam_launch(p, g, m, v, vmax, grad_norm, nullptr, 0, max_norm, grad_scale, n, lr, beta1, beta2, eps, weight_decay, step,
@@ -104,7 +106,7 @@ extern "C" int dcs_adam_amsgrad_step(float* p, const float* g, float* m, float* 
 }
 
 extern "C" int dcs_adam_amsgrad_step_sumsq(float* p, const float* g, float* m, float* v, float* vmax, const double* sumsq_parts,
-                                           int n_parts, float max_norm, float grad_scale, long n, float lr, float beta1,
+                                           int n_parts, float max_norm, float grad_scale, long n, const float* lr, float beta1,
                                            float beta2, float eps, float weight_decay, int step, const int* step_dev,
                                            const float* skip, dcs_stream_t stream) {
     if (n_parts < 1) return DCS_ERR_BADARG;

@@ -436,7 +436,8 @@ class C_NETWORK(LightningModule):
         hp = self.hparams
         optimiser = torch.optim.Adam(self.parameters(), lr=hp['lr'], eps=hp['optim_eps'],
                                      weight_decay=hp['optim_weight_decay'], amsgrad=hp['optim_amsgrad'])
-        scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimiser, patience=10)
+        from .dp import plateau_scheduler
+        scheduler = plateau_scheduler(optimiser)
         return {'optimizer': optimiser, 'lr_scheduler': scheduler,
                 'monitor': 'val_loss' if _mode() in ('dcs', 'drs') else 'speech_loss'}
 

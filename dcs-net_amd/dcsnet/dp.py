@@ -13,6 +13,10 @@ utterances per GPU every rank reproduces the reference's batch-32 semantics (con
                   so the all-reduce and the fused optimizer kernel each touch ONE tensor
   TrainStep       zero-grad -> loss.backward() -> all-reduce -> device-side global norm ->
                   dcs_adam_amsgrad_step (averaging + clip + Adam/AMSGrad in one HIP launch)
+
+The learning rate is the single param group's 'lr' of TrainStep.optimizer (a torch.optim.Optimizer), so the reference's
+ReduceLROnPlateau and SWA's SWALR (dcsnet/swa.py) drive it; the fused kernel reads it from a device scalar that TrainStep
+rewrites, outside any capture, before every step whose rate changed.
 """
 import os
 import torch
@@ -24,6 +28,17 @@ from ._lib import check, ptr, cur_stream
 # built by the reference but never run (c_network.py:160-163 vs :218): their .grad stays None and
 # torch.optim skips them, so they must not be decayed or averaged either
 UNUSED_PREFIXES = ('decoder_attention.12.', 'decoder_attention.13.')
+
+# the reference's learning-rate schedule (c_network.py:229-240, r_network.py:176-182): ReduceLROnPlateau, torch's defaults
+# otherwise (mode min, factor 0.1, threshold 1e-4 relative, cooldown 0); it monitors val_loss in dcs / drs mode and
+# speech_loss in dc / dr mode
+PLATEAU_ARGS = dict(patience=10)
+
+
+def plateau_scheduler(optimizer):
+    """The reference's ReduceLROnPlateau on `optimizer`: C_NETWORK.configure_optimizers and the product training loop
+    (on TrainStep.optimizer, dcsnet/swa.py) both build it here."""
+    return torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, **PLATEAU_ARGS)
 
 
 def hot_parameters(net):
@@ -115,20 +130,54 @@ class FlatBucket:
         return 1
 
 
-class FusedAdam:
+class FusedAdam(torch.optim.Optimizer):
     """dcs_adam_amsgrad_step over a FlatBucket (HIP; no fallback).  The update count also lives on the
-    device so that a captured hipGraph can be replayed while the bias corrections advance."""
+    device so that a captured hipGraph can be replayed while the bias corrections advance.
+
+    A torch.optim.Optimizer with ONE param group over the bucket's parameters, so that stock learning-rate schedulers attach
+    to it: param_groups[0]['lr'] (also `.lr`) is the rate.  The kernels read it from the device scalar `lr_dev`, which
+    sync_lr() rewrites on the current stream when the group's value changed — never inside a capture, where the write would
+    be replayed with the old value.  The other hyper-parameters are read from the instance, as before."""
 
     def __init__(self, bucket, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=0.0):
+        super().__init__(bucket.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_norm))
         self.b = bucket
-        self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
+        self.betas, self.eps, self.wd, self.max_norm = betas, eps, weight_decay, max_norm
         self.m = torch.zeros_like(bucket.flat)
         self.v = torch.zeros_like(bucket.flat)
         self.vmax = torch.zeros_like(bucket.flat)
         self.t = 0
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=bucket.flat.device)
+        # the rate the kernels read; made here, outside any capture, like t_dev
+        self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=bucket.flat.device)
+        self._lr_dev_value = lr
         # fp64 partial sums of g^2 (dcs_grad_sumsq_parts); made here, not in step(): a first step under capture would put it in the graph's pool
         self._parts = torch.empty(512, dtype=torch.float64, device=bucket.flat.device) if bucket.flat.is_cuda else None
+
+    @property
+    def lr(self):
+        return self.param_groups[0]['lr']
+
+    @lr.setter
+    def lr(self, value):
+        self.param_groups[0]['lr'] = value
+
+    def sync_lr(self):
+        """Write param_groups[0]['lr'] into lr_dev on the current stream if it changed since the last write (otherwise: one
+        float comparison).  Called before every step, graph replays included; an unsynchronised rate under capture is an
+        error rather than a rate silently frozen into the graph."""
+        lr = self.param_groups[0]['lr']
+        if lr != self._lr_dev_value:
+            if self.lr_dev.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('FusedAdam: the learning rate changed to %r under stream capture; call sync_lr() before '
+                                   'capturing' % (lr,))
+            self.lr_dev.fill_(lr)
+            self._lr_dev_value = lr
+
+    def zero_grad(self, set_to_none=True):
+        """The bucket's .grad tensors are the gradient sinks the backward kernels write to: they are zeroed in place, never
+        set to None (torch.optim.Optimizer.zero_grad would detach them)."""
+        self.b.zero_grad()
 
     def step(self, world=1, seed_state=None, counters=None):
         """One update, unless the bucket's skip flag is set (a NaN loss on some rank: the reference's trainer skips
@@ -139,6 +188,7 @@ class FusedAdam:
         b = self.b
         if not b.flat.is_cuda:
             raise _lib.DcsHipError('FusedAdam: expected CUDA (HIP) parameters; the HIP path has no CPU fallback')
+        self.sync_lr()
         self.t += 1
         lib = _lib.load()
         nc = 0 if counters is None else counters.numel()
@@ -149,7 +199,7 @@ class FusedAdam:
                                            ptr(seed_state), ptr(counters), nc, cur_stream()), 'dcs_grad_sumsq_parts')
             check(lib.dcs_adam_amsgrad_step_sumsq(ptr(b.flat), ptr(b.grad), ptr(self.m), ptr(self.v), ptr(self.vmax),
                                                   ptr(self._parts), self._parts.numel(), float(self.max_norm), 1.0 / world,
-                                                  b.numel, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t,
+                                                  b.numel, ptr(self.lr_dev), self.betas[0], self.betas[1], self.eps, self.wd, self.t,
                                                   ptr(self.t_dev), ptr(b.skip), cur_stream()), 'dcs_adam_amsgrad_step_sumsq')
         else:
             check(lib.dcs_step_advance_counters(ptr(b.skip), ptr(self.t_dev), ptr(seed_state), ptr(counters), nc, cur_stream()),
@@ -158,8 +208,8 @@ class FusedAdam:
             # kernel as a device scalar (this branch used to pass no norm at all and dropped the clipping silently)
             gn = torch.linalg.vector_norm(b.grad).reshape(1) if self.max_norm > 0 else None
             check(lib.dcs_adam_amsgrad_step(ptr(b.flat), ptr(b.grad), ptr(self.m), ptr(self.v), ptr(self.vmax),
-                                            ptr(gn), float(self.max_norm) if gn is not None else 0.0, 1.0 / world, b.numel, self.lr,
-                                            self.betas[0], self.betas[1], self.eps, self.wd, self.t,
+                                            ptr(gn), float(self.max_norm) if gn is not None else 0.0, 1.0 / world, b.numel,
+                                            ptr(self.lr_dev), self.betas[0], self.betas[1], self.eps, self.wd, self.t,
                                             ptr(self.t_dev), ptr(b.skip), cur_stream()), 'dcs_adam_amsgrad_step')
         # the kernel rewrote the parameters behind torch's version counters: invalidate packed weights
         from . import functional
@@ -175,6 +225,9 @@ class TorchAdam:
         self.b, self.max_norm = bucket, max_norm
         self.opt = torch.optim.Adam(bucket.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                     amsgrad=True)
+
+    def sync_lr(self):
+        """torch.optim.Adam reads param_groups[0]['lr'] itself at every step."""
 
     def step(self, world=1, seed_state=None, counters=None):
         if seed_state is not None:
@@ -227,6 +280,12 @@ class TrainStep:
         # same results; DCS_WGRAD_SIDE=0 keeps the step on one stream (same-box A/B: profiles/r04_side_stream_ab.txt)
         self.wgrad_side_stream = os.environ.get('DCS_WGRAD_SIDE', '1') != '0'
         self.comm_events = None        # bench.py sets a list: (start, end) HIP events around every gradient all-reduce
+
+    @property
+    def optimizer(self):
+        """The torch.optim.Optimizer of the step: its param_groups[0]['lr'] is the learning rate every later step uses (graph
+        replays included), so ReduceLROnPlateau / SWALR attach to it.  FusedAdam is one; TorchAdam wraps torch.optim.Adam."""
+        return self.opt if isinstance(self.opt, torch.optim.Optimizer) else self.opt.opt
 
     def _counting(self, on):
         """While the step's forward runs, the network leaves the `+= 1` of its num_batches_tracked buffers to the optimizer
@@ -376,6 +435,7 @@ class TrainStep:
         """One step through the same launches as a graph replay, issued eagerly and without any host synchronisation
         (measurement harnesses: bench.py brackets individual launches of it with events)."""
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        self.opt.sync_lr()
         loss = self._device_step(batch, world)
         if world > 1:
             world = self.bucket.allreduce(self.comm_events)
@@ -426,6 +486,9 @@ class TrainStep:
         return None if self._static_batch is None else tuple(self._static_batch)
 
     def __call__(self, batch, batch_idx=0):
+        # the optimizer group's learning rate into the device scalar the kernels read, on this stream, before anything of the
+        # step (captured graphs included) is issued — and never inside a capture
+        self.opt.sync_lr()
         if not self.use_graph:
             return self._eager(batch, batch_idx)
         self._calls += 1

@@ -1479,6 +1479,21 @@ def audio_stft_batch(clean, noisy, offsets, index, starts, window, T, hop, scale
     return out
 
 
+# ---- stochastic weight averaging (csrc/swa.hip, dcsnet/swa.py) ---------------------------------------------------------
+
+def swa_average(avg, p, n_averaged):
+    """In place: avg = p when n_averaged == 0, else avg + (p - avg) / (n_averaged + 1) — Lightning 1.5.6's avg_fn, bit for bit
+    its fp32 CPU evaluation (dcs_swa_average_f32).  avg / p: float32 tensors of one size on one device, 16-byte aligned."""
+    _chk(avg, 'avg')
+    _chk(p, 'p')
+    if avg.numel() != p.numel() or avg.device != p.device:
+        raise _lib.DcsHipError(f'swa_average: avg {tuple(avg.shape)} on {avg.device} and p {tuple(p.shape)} on {p.device} differ')
+    if int(n_averaged) < 0:
+        raise _lib.DcsHipError(f'swa_average: n_averaged must be >= 0, got {n_averaged}')
+    check(_lib.load().dcs_swa_average_f32(ptr(avg), ptr(p), avg.numel(), int(n_averaged), cur_stream()), 'dcs_swa_average_f32')
+    return avg
+
+
 # ---- complex <-> channels-last float views -------------------------------------------------
 
 def to_nhwc(z):

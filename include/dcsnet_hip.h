@@ -702,14 +702,15 @@ int dcs_crm_fwd(const float* S, const float* Y, float* M, long n, float eps, dcs
  * (gradient_clip_val 100, train.py:145-146; `grad_norm` = DEVICE scalar holding the 2-norm of the
  * UNSCALED bucket, NULL or max_norm <= 0 disables clipping) and torch.optim.Adam with L2 weight
  * decay and amsgrad (c_network.py:229-234).  step = 1-based update count, or — when step_dev != NULL —
- * read from that device int (so a captured hipGraph can be replayed while the count advances).  All
- * buffers 16-byte aligned, float[n].
+ * read from that device int (so a captured hipGraph can be replayed while the count advances).  lr: a DEVICE
+ * fp32 scalar (ABI 19), read by every launch, so a learning-rate schedule (ReduceLROnPlateau, SWALR) reaches a
+ * replayed graph; the caller writes it outside any capture.  All buffers 16-byte aligned, float[n].
  * skip (device float, may be NULL): when *skip != 0 the launch changes nothing — the device-side form of the
  * reference's NaN-loss guard (training_step returns None and the trainer skips the update, c_network.py:257-261),
  * which a captured step cannot take on the host. */
 int dcs_adam_amsgrad_step(float* p, const float* g, float* m, float* v, float* vmax,
                           const float* grad_norm, float max_norm, float grad_scale, long n,
-                          float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                          const float* lr, float beta1, float beta2, float eps, float weight_decay, int step,
                           const int* step_dev, const float* skip, dcs_stream_t stream);
 /* The global gradient norm without ATen's two launches: dcs_grad_sumsq_parts leaves n_parts (<= 1024) fp64 partial sums of g^2
  * (fixed order: bit-reproducible) and, in the same launch, advances the step's device counters exactly as
@@ -718,8 +719,14 @@ int dcs_adam_amsgrad_step(float* p, const float* g, float* m, float* v, float* v
 int dcs_grad_sumsq_parts(const float* g, long n, double* parts, int n_parts, const float* skip, int* step_dev, long long* seed_dev,
                          long long* counters, int n_counters, dcs_stream_t stream);
 int dcs_adam_amsgrad_step_sumsq(float* p, const float* g, float* m, float* v, float* vmax, const double* sumsq_parts, int n_parts,
-                                float max_norm, float grad_scale, long n, float lr, float beta1, float beta2, float eps,
+                                float max_norm, float grad_scale, long n, const float* lr, float beta1, float beta2, float eps,
                                 float weight_decay, int step, const int* step_dev, const float* skip, dcs_stream_t stream);
+
+/* Stochastic weight averaging (Lightning 1.5.6's StochasticWeightAveraging.avg_fn over the flat bucket): n_averaged == 0
+ * copies p into avg; otherwise avg = avg + (p - avg) / (float)(n_averaged + 1), a true fp32 division (no reciprocal), so the
+ * result is bit for bit torch's fp32 CPU evaluation of the same expression.  avg / p float[n], 16-byte aligned.  Once per
+ * epoch, outside any graph: n_averaged is passed by value. */
+int dcs_swa_average_f32(float* avg, const float* p, long n, long n_averaged, dcs_stream_t stream);
 
 /* The NaN-loss guard of c_network.py:257-261 without a host round trip.
  * dcs_step_guard:   *skip = isnan(*loss) ? 1 : 0.  `skip` is meant to be one extra element of the flat gradient
