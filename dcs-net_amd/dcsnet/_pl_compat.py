@@ -34,6 +34,37 @@ except ImportError:
         def current_epoch(self):
             return 0
 
+        @classmethod
+        def load_from_checkpoint(cls, checkpoint_path, map_location=None, hparams_file=None, **init_kwargs):
+            """Lightning's entry as the reference's test.py calls it (test.py:20-26: config=, seed=, checkpoint_path=,
+            hparams_file=, map_location=): read a checkpoint in Lightning's layout {'state_dict': ..., 'hyper_parameters':
+            ...}, build cls(**init_kwargs), load the state dict strictly, return the module.  `hparams` is the caller's if
+            given, else the checkpoint's hyper_parameters (what save_hyperparameters stored: the flat dict, handed to the
+            constructor's `hparams` argument as Lightning does), else the project's defaults (config.hparams); keys a
+            checkpoint does not hold keep their default.  hparams_file (Lightning's hparams.yaml) replaces the checkpoint's
+            hyper-parameters only when a YAML reader is importable; otherwise it is ignored."""
+            ckpt = torch.load(checkpoint_path, map_location=map_location, weights_only=False)
+            if not isinstance(ckpt, dict) or 'state_dict' not in ckpt:
+                raise KeyError(f"{checkpoint_path}: not a Lightning checkpoint (no 'state_dict')")
+            if 'hparams' not in init_kwargs:
+                from .config import hparams as defaults
+                stored = ckpt.get('hyper_parameters') or {}
+                if hparams_file is not None:
+                    try:
+                        import yaml
+                    except ImportError:
+                        yaml = None
+                    if yaml is not None:
+                        with open(hparams_file) as f:
+                            stored = yaml.safe_load(f) or {}
+                stored = dict(stored)
+                if set(stored) == {'hparams'} and isinstance(stored['hparams'], dict):
+                    stored = dict(stored['hparams'])
+                init_kwargs['hparams'] = {**defaults, **stored}
+            model = cls(**init_kwargs)
+            model.load_state_dict(ckpt['state_dict'], strict=True)
+            return model
+
     def seed_everything(seed):
         import random
         import numpy as np

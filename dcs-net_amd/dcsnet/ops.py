@@ -1479,6 +1479,86 @@ def audio_stft_batch(clean, noisy, offsets, index, starts, window, T, hop, scale
     return out
 
 
+# ---- whole recordings in fixed-shape segments (csrc/enhance.hip, dcsnet/enhance.py) ------------------------------------
+
+def _chk_segment_geometry(what, T, overlap, hop, stitch):
+    T, overlap, hop = int(T), int(overlap), int(hop)
+    if T < 2 or hop <= 0 or hop * (T - 1) <= 256:
+        raise _lib.DcsHipError(f'{what}: T={T}, hop={hop} (need hop (T - 1) > 256)')
+    if stitch and not 2 <= overlap <= T // 2:
+        raise _lib.DcsHipError(f'{what}: overlap={overlap} outside [2, T / 2 = {T // 2}]')
+    if not stitch and not 0 <= overlap < T:
+        raise _lib.DcsHipError(f'{what}: overlap={overlap} outside [0, T = {T})')
+    return T, overlap, hop
+
+
+def audio_stft_segments(noisy, offsets, item, first_frame, window, T, overlap, hop, scale, out=None):
+    """The noisy-only STFT of S segments of a ragged store in one launch (dcs_audio_stft_segments_f32).  noisy float32 [N]:
+    the recordings concatenated, recording u at [offsets[u], offsets[u + 1]) (offsets int64 [n_items + 1] on the device,
+    non-decreasing, offsets[-1] <= N: the caller's invariant).  item / first_frame int32 [S] (device): segment s is frames
+    [first_frame[s], first_frame[s] + T) of recording item[s], zero-extended to hop (Tp - 1) samples, Tp = T + n (T - overlap)
+    the smallest such count that holds it — reflection at the extended recording's two ends only.  -> complex64 [S, 256, T], bit
+    for bit audio_stft_batch's frames of the whole extended recording (n_fft = 512 only).  An item outside [0, n_items), a
+    negative frame or a window past Tp gives zeros for that segment.  out: a contiguous complex64 [S, 256, T] tensor to write (a
+    captured graph's static input)."""
+    _chk(noisy, 'noisy', 1)
+    _chk(window, 'window', 1)
+    _chk_index(offsets, 'offsets', torch.int64)
+    _chk_index(item, 'item', torch.int32)
+    S = item.numel()
+    _chk_index(first_frame, 'first_frame', torch.int32, S)
+    if window.numel() != 512:
+        raise _lib.DcsHipError(f'audio_stft_segments: n_fft = 512 only, got a window of {window.numel()}')
+    if offsets.numel() < 2:
+        raise _lib.DcsHipError(f'audio_stft_segments: {offsets.numel()} offsets')
+    T, overlap, hop = _chk_segment_geometry('audio_stft_segments', T, overlap, hop, stitch=False)
+    if S == 0 or S > 65535:
+        raise _lib.DcsHipError(f'audio_stft_segments: S={S} (need 1 <= S <= 65535)')
+    dev = noisy.device
+    if out is None:
+        out = torch.empty((S, 256, T), dtype=torch.complex64, device=dev)
+    elif out.dtype != torch.complex64 or tuple(out.shape) != (S, 256, T) or not out.is_contiguous() or out.device != dev:
+        raise _lib.DcsHipError(f'audio_stft_segments: out must be a contiguous complex64 [{S}, 256, {T}] on {dev}')
+    for t in (offsets, item, first_frame, window):
+        if t.device != dev:
+            raise _lib.DcsHipError(f'audio_stft_segments: every tensor on {dev}')
+    check(_lib.load().dcs_audio_stft_segments_f32(ptr(noisy), ptr(offsets), offsets.numel() - 1, ptr(item), ptr(first_frame), S,
+                                                  ptr(window), 512, T, overlap, hop, float(scale), ptr(out), cur_stream()),
+          'dcs_audio_stft_segments_f32')
+    return out
+
+
+def segments_stitch(seg, seg_first, offsets, total, T, overlap, hop, out=None, pcm=False):
+    """Segment waveforms -> one waveform per recording (dcs_segments_stitch_f32).  seg float32 [rows, hop (T - 1)]; recording u
+    owns rows [seg_first[u], seg_first[u + 1]) (int32 [n_items + 1], device), its segment s starting at sample
+    s (T - overlap) hop, and the output samples [offsets[u], offsets[u + 1]) (int64 [n_items + 1], device; total = offsets[-1],
+    known to the caller: no read-back).  The hop (overlap - 1) samples two segments share are cross-faded linearly
+    (a + w (b - a), w = (j + 0.5) / n); every other sample is its segment's, unchanged.  -> float32 [total]; with pcm=True
+    (float32 [total], int16 [total]), the second the first times 32768, rounded to nearest, clipped to +-32767.
+    out: the float destination."""
+    _chk(seg, 'seg', 2)
+    _chk(out, 'out', 1)
+    _chk_index(seg_first, 'seg_first', torch.int32)
+    _chk_index(offsets, 'offsets', torch.int64, seg_first.numel())
+    T, overlap, hop = _chk_segment_geometry('segments_stitch', T, overlap, hop, stitch=True)
+    total = int(total)
+    if seg_first.numel() < 2 or total < 0 or seg.shape[0] == 0 or seg.shape[1] != hop * (T - 1):
+        raise _lib.DcsHipError(f'segments_stitch: seg {tuple(seg.shape)} for T={T}, hop={hop}; {seg_first.numel()} seg_first, '
+                               f'total={total}')
+    dev = seg.device
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=dev)
+    elif out.numel() != total:
+        raise _lib.DcsHipError(f'segments_stitch: out of {out.numel()} samples for total={total}')
+    for t in (seg_first, offsets, out):
+        if t.device != dev:
+            raise _lib.DcsHipError(f'segments_stitch: every tensor on {dev}')
+    pcm_out = torch.empty(total, dtype=torch.int16, device=dev) if pcm else None
+    check(_lib.load().dcs_segments_stitch_f32(ptr(seg), seg.shape[0], ptr(seg_first), ptr(offsets), seg_first.numel() - 1, total, T,
+                                              overlap, hop, ptr(out), ptr(pcm_out), cur_stream()), 'dcs_segments_stitch_f32')
+    return (out, pcm_out) if pcm else out
+
+
 # ---- stochastic weight averaging (csrc/swa.hip, dcsnet/swa.py) ---------------------------------------------------------
 
 def swa_average(avg, p, n_averaged):

@@ -859,6 +859,30 @@ int dcs_audio_stft_batch_f32(const float* clean, const float* noisy, const long*
                              const int* item_start, int B, const float* window, int n_fft, int T, int hop, float scale,
                              float* out_noise, float* out_noisy, float* out_clean, dcs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Whole recordings through a fixed-shape pass (dcsnet/enhance.py), enhance.hip (ABI 20).  A recording of len samples is
+ * treated as zero-extended to L = hop (Tp - 1) samples, Tp = T + n (T - overlap) for the smallest n >= 0 with L >= len; it has
+ * n + 1 segments of T frames, segment s at frame s (T - overlap) and at sample s (T - overlap) hop, hop (T - 1) samples long.
+ * dcs_audio_stft_segments_f32: the noisy-only STFT of S segments in one launch.  noisy float[offsets[n_items]]: recording u is
+ *   [offsets[u], offsets[u + 1]) (int64 offsets on the device).  seg_item / seg_first_frame int[S] on the device: segment s is
+ *   frames [seg_first_frame[s], seg_first_frame[s] + T) of the centred STFT of the extended recording seg_item[s] (reflection
+ *   at 0 and at L only, zero at or past len).  out complex[S][256][T]: per element the arithmetic of dcs_audio_stft_batch_f32,
+ *   i.e. bit for bit the frames that call makes of the whole extended recording (T = Tp, start 0).  An item outside
+ *   [0, n_items), a negative first frame or a window leaving [0, Tp) gives zeros for that segment and reads nothing.
+ *   n_fft = 512 only, hop (T - 1) > 256, 0 <= overlap < T, S <= 65535.  No sync.
+ * dcs_segments_stitch_f32: seg float[seg_rows][hop (T - 1)] segment waveforms -> y float[total_out], recording u at
+ *   [offsets[u], offsets[u + 1]) (total_out = offsets[n_items]) from rows [seg_first[u], seg_first[u + 1]) (int[n_items + 1] on the
+ *   device).  Where two segments overlap (n = hop (overlap - 1) samples) sample j of the overlap is a + w (b - a),
+ *   w = (j + 0.5f) / n, a the earlier and b the later segment's sample; elsewhere the covering segment's sample unchanged.
+ *   2 <= overlap <= T / 2 (at most two owners per sample).  pcm (may be null) short[total_out]: the same samples times 32768,
+ *   rounded to nearest even, clipped to +-32767.  One thread per sample, plain stores: bit-reproducible.  Rows a table does not
+ *   cover (outside [0, seg_rows), too few segments) give zeros; nothing outside seg is read.  No sync. */
+int dcs_audio_stft_segments_f32(const float* noisy, const long* offsets, int n_items, const int* seg_item,
+                                const int* seg_first_frame, int S, const float* window, int n_fft, int T, int overlap, int hop,
+                                float scale, float* out, dcs_stream_t stream);
+int dcs_segments_stitch_f32(const float* seg, long seg_rows, const int* seg_first, const long* offsets, int n_items,
+                            long total_out, int T, int overlap, int hop, float* y, short* pcm, dcs_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * bf16 activation storage (BASELINE.json configs[4]: bf16 activations in HBM, fp32 accumulation / statistics / parameters /
  * optimizer; the reference itself trains at precision 32: config.py:70, train.py:144 — this is the build's stated
