@@ -270,6 +270,99 @@ __global__ __launch_bounds__(kThreads) void bound2_apply_polar_frames_bwd_kernel
     }
 }
 
+// ---- The real twin (DR-Net / DRS-Net, network_functions.py:224-232): sigmoid mask on |Y|, the noisy phase kept ---------------------
+// |Y| as the network's input (torch.abs of a complex tensor is hypot: no overflow at 1e19-sized components)
+__global__ __launch_bounds__(kThreads) void complex_abs_kernel(const float2* __restrict__ Y, float* __restrict__ out, long n) {
+    for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
+        const float2 y = Y[i];
+        out[i] = hypotf(y.x, y.y);
+    }
+}
+
+__device__ __forceinline__ float sigmoid1(float d) { return 1.f / (1.f + expf(-d)); }
+
+// The step function's mask multiply, magnitude subtraction and mag_phase_2_wave's cos / sin of the noisy phase, fused with the
+// zero bin and the frame-major transpose of the synthesis: m = sigmoid(D), a = |y|, u = unit(y_r + eps, y_i), n = a m;
+// out[b] = n u and, PAIR, out[B + b] = (a - n) u (the reference subtracts magnitudes).
+// grid (ceil(T/32), ceil(Fp/32), B); block 32 x 8.  Y: complex[B][F][T]; D: float[B][F][T] (the last stage's output BEFORE its
+// sigmoid); out: complex[(PAIR ? 2B : B)][T][Fp] (bins >= F are zero); Mout: optional float[B][F][T]
+template <bool PAIR>
+__global__ __launch_bounds__(kThreads) void rmask_apply_polar_frames_kernel(const float2* __restrict__ Y, const float* __restrict__ D,
+                                                                             float* __restrict__ Mout, float2* __restrict__ out,
+                                                                             int B, int F, int Fp, int T, float eps) {
+    __shared__ float2 tn[32][33], ts[PAIR ? 32 : 1][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int t0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
+    const long b = blockIdx.z;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int f = f0 + ty + 8 * r, t = t0 + tx;
+        float2 on = make_float2(0.f, 0.f), os = on;
+        if (f < F && t < T) {
+            const long i = (b * F + f) * T + t;
+            const float2 y = Y[i];
+            const float m = sigmoid1(D[i]);
+            const float a = hypotf(y.x, y.y);
+            const float2 u = unit_dir(y.x + eps, y.y);
+            const float n = a * m, s = a - n;
+            if (Mout) Mout[i] = m;
+            on = make_float2(n * u.x, n * u.y);
+            os = make_float2(s * u.x, s * u.y);
+        }
+        tn[ty + 8 * r][tx] = on;
+        if (PAIR) ts[ty + 8 * r][tx] = os;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int t = t0 + ty + 8 * r, f = f0 + tx;
+        if (t < T && f < Fp) {
+            out[(b * T + t) * Fp + f] = tn[tx][ty + 8 * r];
+            if (PAIR) out[((b + B) * T + t) * Fp + f] = ts[tx][ty + 8 * r];
+        }
+    }
+}
+
+// g: complex[(PAIR ? 2B : B)][T][Fp] cotangent of the spectra (herm: see bound2_apply_polar_frames_bwd_kernel); gM: optional
+// float[B][F][T]; gD: float[B][F][T] = m (1 - m) (a u.(g_n - g_s) + g_M), the forward recomputed from (Y, D)
+template <bool PAIR>
+__global__ __launch_bounds__(kThreads) void rmask_apply_polar_frames_bwd_kernel(const float2* __restrict__ Y, const float* __restrict__ D,
+                                                                                 const float2* __restrict__ g, const float* __restrict__ gM,
+                                                                                 float* __restrict__ gD, int B, int F, int Fp, int T,
+                                                                                 float eps, int herm) {
+    __shared__ float2 tg[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int t0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
+    const long b = blockIdx.z;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int t = t0 + ty + 8 * r, f = f0 + tx;
+        float2 d = make_float2(0.f, 0.f);
+        if (t < T && f < F) {
+            d = g[(b * T + t) * Fp + f];
+            if (PAIR) { const float2 s = g[((b + B) * T + t) * Fp + f]; d.x -= s.x; d.y -= s.y; }     // n = a m, s = a - n
+        }
+        tg[tx][ty + 8 * r] = d;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int f = f0 + ty + 8 * r, t = t0 + tx;
+        if (f < F && t < T) {
+            const long i = (b * F + f) * T + t;
+            const float2 y = Y[i];
+            const float m = sigmoid1(D[i]);
+            const float a = hypotf(y.x, y.y);
+            const float2 u = unit_dir(y.x + eps, y.y);
+            float2 d = tg[ty + 8 * r][tx];
+            if (herm && f > 0 && f < Fp - 1) { d.x *= 2.f; d.y *= 2.f; }
+            float gm = a * (u.x * d.x + u.y * d.y);
+            if (gM) gm += gM[i];
+            gD[i] = m * (1.f - m) * gm;
+        }
+    }
+}
+
 inline int ew_grid(long n) {
     long nb = (n + kThreads * 4 - 1) / (kThreads * 4);
     return (int)(nb < 1 ? 1 : (nb > 2048 ? 2048 : nb));
@@ -383,6 +476,46 @@ extern "C" int dcs_bound2_apply_polar_frames_bwd(const float* Y, const float* D_
         DCS_LAUNCH(bound2_apply_polar_frames_bwd_kernel<false>, grid, dim3(kThreads), 0, dcs_stream(stream), (const float2*)Y,
                    (const float2*)D_raw, (const float2*)g_out, (const float2*)g_M, (float2*)g_D, B, F, Fp, T, eps, hermitian, 0.f,
                    (uint64_t)0, (const uint64_t*)nullptr);
+    DCS_CHECK_LAUNCH();
+    return DCS_OK;
+}
+
+// |Y| of complex[n]: the real network's input (network_functions.py:225, torch.abs)
+extern "C" int dcs_complex_abs_f32(const float* Y, float* out, long n, dcs_stream_t stream) {
+    if (!Y || !out || n <= 0) return DCS_ERR_BADARG;
+    DCS_LAUNCH(complex_abs_kernel, dim3(ew_grid(n)), dim3(kThreads), 0, dcs_stream(stream), (const float2*)Y, out, n);
+    DCS_CHECK_LAUNCH();
+    return DCS_OK;
+}
+
+// (Y, the real network's last-stage output D before its sigmoid) -> the frame-major spectra of the magnitude-masked estimates
+// on the noisy phase (network_functions.py:229-232 + mag_phase_2_wave's polar form): out complex[(pair ? 2B : B)][T][Fp], rows
+// [0, B) from |Y| m, with pair rows [B, 2B) from |Y| - |Y| m; Fp >= F, bins >= F zero.  M_out: optional float[B][F][T] = sigmoid(D).
+extern "C" int dcs_rmask_apply_polar_frames_fwd(const float* Y, const float* D, float* M_out, float* out, int B, int F, int Fp, int T,
+                                                float eps, int pair, dcs_stream_t stream) {
+    if (!Y || !D || !out || B <= 0 || B > 65535 || F <= 0 || Fp < F || T <= 0) return DCS_ERR_BADARG;
+    const dim3 grid((T + 31) / 32, (Fp + 31) / 32, B);
+    if (pair)
+        DCS_LAUNCH(rmask_apply_polar_frames_kernel<true>, grid, dim3(kThreads), 0, dcs_stream(stream), (const float2*)Y, D, M_out,
+                   (float2*)out, B, F, Fp, T, eps);
+    else
+        DCS_LAUNCH(rmask_apply_polar_frames_kernel<false>, grid, dim3(kThreads), 0, dcs_stream(stream), (const float2*)Y, D, M_out,
+                   (float2*)out, B, F, Fp, T, eps);
+    DCS_CHECK_LAUNCH();
+    return DCS_OK;
+}
+
+// g_D from the cotangent g_out of those spectra (hermitian as in dcs_polar_frames_bwd) and, optionally, the cotangent g_M of the mask
+extern "C" int dcs_rmask_apply_polar_frames_bwd(const float* Y, const float* D, const float* g_out, const float* g_M, float* g_D,
+                                                int B, int F, int Fp, int T, float eps, int hermitian, int pair, dcs_stream_t stream) {
+    if (!Y || !D || !g_out || !g_D || B <= 0 || B > 65535 || F <= 0 || Fp < F || T <= 0) return DCS_ERR_BADARG;
+    const dim3 grid((T + 31) / 32, (F + 31) / 32, B);
+    if (pair)
+        DCS_LAUNCH(rmask_apply_polar_frames_bwd_kernel<true>, grid, dim3(kThreads), 0, dcs_stream(stream), (const float2*)Y, D,
+                   (const float2*)g_out, g_M, g_D, B, F, Fp, T, eps, hermitian);
+    else
+        DCS_LAUNCH(rmask_apply_polar_frames_bwd_kernel<false>, grid, dim3(kThreads), 0, dcs_stream(stream), (const float2*)Y, D,
+                   (const float2*)g_out, g_M, g_D, B, F, Fp, T, eps, hermitian);
     DCS_CHECK_LAUNCH();
     return DCS_OK;
 }

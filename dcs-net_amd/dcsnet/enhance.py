@@ -5,6 +5,7 @@
                                                         -> list of 1-D float32 device tensors at config.sr
     speech, noise = enh(waves, 48000, return_noise=True)
     enh.enhance_files(in_paths, out_paths)             mono 16-bit PCM in, mono 16-bit PCM at config.sr out
+    enh = MagnitudeEnhancer(rnet, mode='drs', ...)     the same for the real twin (R_NETWORK: DRS-Net 'drs', DR-Net 'dr')
 
 The network's forward runs at any number of frames, but a pass at a recording's own length is a few hundred launches bound
 by latency and no captured graph survives a shape change.  So every recording is cut into segments of `segment_frames` frames
@@ -67,13 +68,20 @@ class Enhancer:
     of 8 (the network's time strides); 2 <= overlap_frames <= segment_frames / 2.  The network's activation dtype is followed
     as is (set_activation_dtype); its training flag is restored when a call returns."""
 
+    MODES = ('dcs', 'dc')                 # (subtractive: speech and noise estimates, mask applied: speech only)
+
+    @staticmethod
+    def _check_network(net):
+        if getattr(net, '_step_dtype', None) != 'complex' or not getattr(net, 'supports_unbounded_forward', False):
+            raise DcsHipError('Enhancer: the complex network (C_NETWORK) only — the real twin (R_NETWORK) goes through '
+                              'MagnitudeEnhancer')
+
     def __init__(self, net, mode='dcs', segment_frames=2000, overlap_frames=300, batch_segments=16, use_graph=True,
                  chunk_samples=1 << 24):
-        if mode not in ('dcs', 'dc'):
-            raise ValueError(f"Enhancer: mode {mode!r}: 'dcs' (subtractive) or 'dc' (mask applied)")
-        if getattr(net, '_step_dtype', None) != 'complex' or not getattr(net, 'supports_unbounded_forward', False):
-            raise DcsHipError('Enhancer: the complex network (C_NETWORK) only — the real twin (R_NETWORK) still runs its mask '
-                              'and synthesis in ATen')
+        if mode not in self.MODES:
+            raise ValueError(f"{type(self).__name__}: mode {mode!r}: {self.MODES[0]!r} (subtractive) or {self.MODES[1]!r} "
+                             f"(mask applied)")
+        self._check_network(net)
         cfg = net.config
         if int(cfg.fft_size) != 512 or int(cfg.window_length) != 512:
             raise DcsHipError(f'Enhancer: n_fft = 512 only, got {cfg.fft_size}')
@@ -184,7 +192,7 @@ class Enhancer:
     def _state_key(self):
         net = self.net
         tensors = list(net.parameters()) + list(net.buffers())
-        return (F.state_generation(), ops.conv_precision(), net.activation_dtype, self._batch_step, self._store.data_ptr(),
+        return (F.state_generation(), ops.conv_precision(), getattr(net, 'activation_dtype', None), self._batch_step, self._store.data_ptr(),
                 self._offsets.data_ptr(), tuple((id(t), t._version, t.data_ptr()) for t in tensors))
 
     def _step_fn(self):
@@ -198,12 +206,7 @@ class Enhancer:
             for _ in range(2):
                 self._run_batch()
             torch.cuda.synchronize(self.device)
-            from . import complexLayers
-            # references, not copies: the graph reads these allocations, the caches that own them may drop them
-            mods = list(self.net.modules())
-            self._keep = (list(F._pack_cache.values()),
-                          [complexLayers._EVAL_COEF.get(m) for m in mods if isinstance(m, complexLayers.ComplexBatchNorm2d)],
-                          [dict(F._LSTM_EVAL_OPERANDS.get(m, {})) for m in mods if isinstance(m, torch.nn.LSTM)])
+            self._keep = self._cached_operands()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 out = self._run_batch()
@@ -213,6 +216,15 @@ class Enhancer:
             self._graph.replay()
             return self._graph_out
         return replay
+
+    def _cached_operands(self):
+        """References, not copies, to what the warm-up passes left in the package's caches: the graph reads these allocations,
+        the caches that own them may drop them."""
+        from . import complexLayers
+        mods = list(self.net.modules())
+        return (list(F._pack_cache.values()),
+                [complexLayers._EVAL_COEF.get(m) for m in mods if isinstance(m, complexLayers.ComplexBatchNorm2d)],
+                [dict(F._LSTM_EVAL_OPERANDS.get(m, {})) for m in mods if isinstance(m, torch.nn.LSTM)])
 
     # ---- public --------------------------------------------------------------------------------------------------------
 
@@ -226,7 +238,7 @@ class Enhancer:
         sel, seg_first, offsets = self._upload_tables(plan)
         rows = plan.batches * self.S
         speech = torch.empty((rows, self.Ls), dtype=torch.float32, device=self.device)
-        noise = torch.empty_like(speech) if self.mode == 'dcs' else None
+        noise = torch.empty_like(speech) if self.mode == self.MODES[0] else None
         try:
             net.eval()
             with torch.no_grad():
@@ -252,8 +264,8 @@ class Enhancer:
         return [flat[int(a):int(b)] for a, b in zip(plan.offsets[:-1], plan.offsets[1:])]
 
     def __call__(self, waves, sample_rate, return_noise=False):
-        if return_noise and self.mode != 'dcs':
-            raise ValueError("Enhancer: mode 'dc' applies the mask and has no noise estimate")
+        if return_noise and self.mode != self.MODES[0]:
+            raise ValueError(f"{type(self).__name__}: mode {self.mode!r} applies the mask and has no noise estimate")
         plan, tables, noise, speech = self.enhance_segments(waves, sample_rate)
         out = self._split(plan, self.stitch(plan, tables, speech))
         if return_noise:
@@ -282,3 +294,33 @@ class Enhancer:
         for p, a, b in zip(out_paths, plan.offsets[:-1], plan.offsets[1:]):
             wavfile.write(p, self.sr, pcm[int(a):int(b)])
         return out_paths
+
+
+class MagnitudeEnhancer(Enhancer):
+    """The Enhancer of the real twin.  net: an R_NETWORK on a CUDA (HIP) device.  mode: 'drs' (DRS-Net: the noise magnitude
+    |Y| M is subtracted from |Y|) or 'dr' (DR-Net: the mask is applied, no noise estimate); both estimates keep the noisy
+    phase (network_functions.py:224-232, :261-267).  Per batch of segments: ops.complex_abs(Y), the network's raw last-stage
+    output (forward(sigmoid=False)), then sigmoid, mask, subtraction and synthesis as one fused pass
+    (F.rmask_apply_polar_wave).  Planner, segment STFT, stitch, graph lifetime and keying are the Enhancer's."""
+
+    MODES = ('drs', 'dr')
+
+    def __init__(self, net, mode='drs', *args, **kw):
+        super().__init__(net, mode, *args, **kw)
+
+    @staticmethod
+    def _check_network(net):
+        if getattr(net, '_step_dtype', None) != 'real' or not getattr(net, 'supports_raw_forward', False):
+            raise DcsHipError('MagnitudeEnhancer: the real network (R_NETWORK) only — the complex network (C_NETWORK) goes '
+                              'through Enhancer')
+
+    def _batch_step(self, Y):
+        """Y complex64 [S, 256, T] -> waveforms [2 S, hop (T - 1)] ('drs': rows [0, S) the noise, [S, 2 S) the speech
+        estimates) or [S, hop (T - 1)] ('dr': speech)."""
+        d_raw = self.net(ops.complex_abs(Y), sigmoid=False).reshape(Y.shape)       # (forward squeezes a batch of one)
+        return F.rmask_apply_polar_wave(Y, d_raw, self.window, self.inv_env, 512, self.hop, self.synth_scale, self.eps,
+                                        pair=self.mode == 'drs', want_mask=False)[1]
+
+    def _cached_operands(self):
+        from . import r_network
+        return (list(F._pack_cache.values()), [e[2] for e in r_network._PACKS.values()])

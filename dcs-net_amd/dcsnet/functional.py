@@ -1217,6 +1217,51 @@ def bound2_apply_polar_wave_pair(Y, D_raw, window, inv_env, n_fft, hop, scale, e
     return (None if M is None else torch.view_as_complex(M)), wave
 
 
+class _RMaskApplyPolarWaveFn(torch.autograd.Function):
+    """(Y, the real network's last-stage output D before its sigmoid) -> (sigmoid mask or None, waveforms [2B or B, L]): the mask
+    multiply, the magnitude subtraction and mag_phase_2_wave on the noisy phase (network_functions.py:229-232, :140-150) as ONE node
+    built like _Bound2ApplyPolarWaveFn — the magnitudes, the phase and the estimates never exist in HBM; the backward recomputes
+    them from (Y, D)."""
+
+    @staticmethod
+    def forward(ctx, Y, D, window, inv_env, n_fft, hop, scale, eps, pair, want_mask):
+        B, Fb, T, _ = Y.shape
+        if Fb + 1 != n_fft // 2 + 1 or n_fft != 512:
+            raise DcsHipError(f'rmask_apply_polar_wave: {Fb} bins, n_fft = {n_fft}: the fused form is built for n_fft = 512')
+        M, comp = ops.rmask_apply_polar_frames(Y, D, Fb + 1, eps, pair, want_mask)
+        ctx.cfg = ((comp.shape[0], T, n_fft), hop, scale / n_fft, eps, pair)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(Y, D, window, inv_env)
+        if ops.irfft512_ola_ok(T, hop):
+            return M, ops.irfft512_ola(comp, window, inv_env, hop, scale / n_fft)
+        return M, ops.istft_ola(ops.irfft512(comp), window, inv_env, hop, scale / n_fft)
+
+    @staticmethod
+    def backward(ctx, gM, g):
+        Y, D, window, inv_env = ctx.saved_tensors
+        shape, hop, scale, eps, pair = ctx.cfg
+        if g is None and gM is None:
+            return (None,) * 10
+        if g is None:                                       # the mask's cotangent alone: the same kernel over a zero spectrum
+            G = torch.zeros((shape[0], shape[1], Y.shape[1] + 1, 2), dtype=torch.float32, device=Y.device)
+        elif hop & 1:
+            G = ops.rfft512(ops.istft_ola(shape, window, inv_env, hop, scale, grad=g.contiguous()))
+        else:
+            G = ops.rfft512_ola(g.contiguous(), window, inv_env, shape[1], hop, scale)     # [2B or B, T, 257, 2]; the frames are not stored
+        gD = ops.rmask_apply_polar_frames(Y, D, Y.shape[1] + 1, eps, pair, grad=G, g_M=None if gM is None else gM.contiguous(),
+                                          hermitian=True)
+        return (None, gD) + (None,) * 8
+
+
+def rmask_apply_polar_wave(Y, D, window, inv_env, n_fft, hop, scale, eps=10e-7, pair=True, want_mask=False):
+    """Complex Y [B, F, T], float D [B, F, T] (R_NETWORK.forward(|Y|, sigmoid=False)) -> (M = sigmoid(D) float [B, F, T] or None,
+    waveforms float [2B or B, hop (T - 1)]): rows [0, B) from the magnitude |Y| M on the noisy phase — the noise estimate of 'drs',
+    the speech estimate of 'dr' (pair=False) — and with pair rows [B, 2B) from |Y| - |Y| M, the speech estimate of 'drs'
+    (network_functions.py:229-232, :265-267); differentiable w.r.t. D only."""
+    y = torch.view_as_real(Y.contiguous())
+    return _RMaskApplyPolarWaveFn.apply(y, D.contiguous(), window, inv_env, n_fft, hop, scale, eps, bool(pair), bool(want_mask))
+
+
 class _SiSNRFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, clean, est, eps):

@@ -9,6 +9,7 @@ spectrum, 512-point inverse real FFT (csrc/fft512.hip), window / overlap-add / e
 the configured loss pair (csrc/synth.hip).  On PyTorch-ROCm: the non-configured loss types (wSDR, L1, MSE reductions)
 and, for n_fft != 512 only, the inverse FFT (rocFFT via torch.fft.irfft).
 """
+import os
 import sys
 
 import torch
@@ -366,11 +367,45 @@ def _complex_step(self, noise_data, noisy_data, clean_data, need_noisy_audio=Fal
     return audio
 
 
+# The real twin's train step through the fused mask + synthesis node (_real_step_fused).  DCS_RSTEP_FUSED=0 keeps the op-by-op
+# spelling reachable: for A/B runs (tools/rstep_bench.py) and for the tests that compare the two.
+RSTEP_FUSED = os.environ.get('DCS_RSTEP_FUSED', '1') != '0'
+
+
+def _real_step_fused(self, noise_data, noisy_data, clean_data, pair):
+    """The 'drs' (pair) / 'dr' train step with |noisy| from one kernel, the network's raw last-stage output, and the sigmoid, the
+    mask multiply, the magnitude subtraction and the synthesis on the noisy phase as ONE autograd node
+    (F.rmask_apply_polar_wave): no abs / atan2 / cos / sin / complex / pad / transpose / irfft tensors in HBM.  Both targets are
+    synthesised as one batch of 2B signals; with pair the estimates are too (rows [0,B) noise, [B,2B) speech) and calc_loss gets
+    the stacked signals, as from _complex_step_pair.  Same arithmetic per signal as _real_step."""
+    eps = self.hparams['atan2_eps']
+    cfg = self.config
+    B = noisy_data.shape[0]
+    tw = _polar_wave(_stacked(noise_data, clean_data), eps, cfg)
+    d_raw = self(ops.complex_abs(noisy_data), sigmoid=False)
+    if d_raw.dim() + 1 == noisy_data.dim() and B == 1:          # the B = 1 squeeze quirk (r_network.py:173)
+        d_raw = d_raw.unsqueeze(0)
+    window = _window_on(cfg, noisy_data.device)
+    scale = float(cfg.fft_size) ** 0.5 if cfg.normalise_stft else 1.0
+    # the sigmoid mask itself is read by the mask-domain losses only (noise_loss_type 0, 2, 4, 5), never on this path: not stored
+    mask, ew = F.rmask_apply_polar_wave(noisy_data, d_raw, window, _inv_envelope(window, noisy_data.shape[2], cfg.hop_length),
+                                        cfg.fft_size, cfg.hop_length, scale, eps, pair=pair, want_mask=False)
+    if not pair:
+        return {'noise_audio': tw[:B], 'clean_audio': tw[B:], 'predict_clean_audio': ew}
+    return {'noise_audio': tw[:B], 'clean_audio': tw[B:], 'predict_noise_mask': mask,
+            'predict_noise_audio': ew[:B], 'predict_clean_audio': ew[B:], '_pair': (tw, ew)}
+
+
 def _real_step(self, noise_data, noisy_data, clean_data, need_noisy_audio=False):
     """dtype == "real" (DRS / DR-Net, network_functions.py:224-232, :261-267): the network sees |noisy| and returns a
     sigmoid mask; the estimates keep the noisy phase."""
     eps = self.hparams['atan2_eps']
     cfg = self.config
+    pair = _mode() in ('dcs', 'drs')
+    if (RSTEP_FUSED and not need_noisy_audio and (self.hparams.get('noise_loss_type') == 6 or not pair) and
+            noisy_data.is_cuda and noise_data.shape == noisy_data.shape == clean_data.shape and noisy_data.dim() == 3 and
+            noisy_data.shape[1] == 256 and cfg.fft_size == 512 and getattr(self, 'supports_raw_forward', False)):
+        return _real_step_fused(self, noise_data, noisy_data, clean_data, pair)
     audio = {'noise_audio': _polar_wave(noise_data, eps, cfg), 'clean_audio': _polar_wave(clean_data, eps, cfg)}
     if need_noisy_audio or self.hparams.get('noise_loss_type') in (1, 3, 4, 5):
         audio['noisy_audio'] = _polar_wave(noisy_data, eps, cfg)

@@ -989,6 +989,51 @@ def bound2_apply_polar_frames(Y, D_raw, Fp, eps=10e-7, drop_p=0.0, seed=0, want_
     return g
 
 
+def complex_abs(Y):
+    """dcs_complex_abs_f32: |Y| (hypot) of a complex64 tensor, or of its float [..., 2] view -> float32 of Y's complex shape: the real
+    network's input (network_functions.py:225)."""
+    if Y.is_complex():
+        if not Y.is_cuda:
+            raise _lib.DcsHipError('complex_abs: expected a CUDA (HIP) tensor; the HIP path has no CPU fallback')
+        if Y.dtype != torch.complex64:
+            raise _lib.DcsHipError(f'complex_abs: expected complex64, got {Y.dtype}')
+        Y = torch.view_as_real(Y.contiguous())
+    _chk(Y, 'Y')
+    if Y.dim() < 1 or Y.shape[-1] != 2 or Y.numel() == 0:
+        raise _lib.DcsHipError(f'complex_abs: expected (re, im) pairs, got shape {tuple(Y.shape)}')
+    out = torch.empty(Y.shape[:-1], dtype=torch.float32, device=Y.device)
+    check(_lib.load().dcs_complex_abs_f32(ptr(Y), ptr(out), out.numel(), cur_stream()), 'dcs_complex_abs_f32')
+    return out
+
+
+def rmask_apply_polar_frames(Y, D, Fp, eps=10e-7, pair=True, want_mask=False, grad=None, g_M=None, hermitian=False):
+    """dcs_rmask_apply_polar_frames_fwd / _bwd: Y float [B,F,T,2], D float [B,F,T] (the real network's last-stage output before its
+    sigmoid).  Forward (grad None): (M = sigmoid(D) or None, out [(2B if pair else B),T,Fp,2]) — the frame-major spectra of |Y| M on
+    the noisy phase (rows [0, B)) and, with pair, of |Y| - |Y| M (rows [B, 2B)).  With grad of that shape (and optionally g_M
+    [B,F,T]): the cotangent of D."""
+    _chk(Y, 'Y', 4)
+    _chk(D, 'D', 3)
+    if tuple(Y.shape) != tuple(D.shape) + (2,):
+        raise _lib.DcsHipError(f'rmask_apply_polar_frames: Y {tuple(Y.shape)} vs D {tuple(D.shape)}')
+    B, F, T, _ = Y.shape
+    rows = 2 * B if pair else B
+    lib = _lib.load()
+    if grad is None:
+        out = torch.empty((rows, T, Fp, 2), dtype=torch.float32, device=Y.device)
+        M = torch.empty_like(D) if want_mask else None
+        check(lib.dcs_rmask_apply_polar_frames_fwd(ptr(Y), ptr(D), ptr(M), ptr(out), B, F, Fp, T, eps, int(bool(pair)), cur_stream()),
+              'dcs_rmask_apply_polar_frames_fwd')
+        return M, out
+    _chk(grad, 'grad', 4)
+    _chk(g_M, 'g_M', 3)
+    if tuple(grad.shape) != (rows, T, Fp, 2) or (g_M is not None and g_M.shape != D.shape):
+        raise _lib.DcsHipError(f'rmask_apply_polar_frames: grad {tuple(grad.shape)} for B={B}, T={T}, Fp={Fp}, pair={bool(pair)}')
+    g = torch.empty_like(D)
+    check(lib.dcs_rmask_apply_polar_frames_bwd(ptr(Y), ptr(D), ptr(grad), ptr(g_M), ptr(g), B, F, Fp, T, eps, int(bool(hermitian)),
+                                               int(bool(pair)), cur_stream()), 'dcs_rmask_apply_polar_frames_bwd')
+    return g
+
+
 def polar_frames(z, Fp, eps=10e-7, grad=None, hermitian=False):
     """z: float [B,F,T,2].  Forward (grad None): FRAME-MAJOR [B,T,Fp,2] = |z| unit(z_r+eps, z_i), zero bins F..Fp-1.
     With grad [B,T,Fp,2]: the cotangent of z (hermitian: grad is the plain rfft of an unnormalised irfft's output

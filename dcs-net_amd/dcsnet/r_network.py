@@ -540,7 +540,11 @@ class R_NETWORK(LightningModule):
         return y
 
     # ---- forward (r_network.py:140-173) ---------------------------------------------------------------------------
-    def forward(self, x):
+    supports_raw_forward = True          # forward(x, sigmoid=False): the step functions fuse the sigmoid into the mask kernel
+
+    def forward(self, x, sigmoid=True):
+        """sigmoid=False: the squeezed last-stage output after its own dropout, without the final torch.sigmoid — for
+        F.rmask_apply_polar_wave, which applies it inside the mask + synthesis kernel."""
         hp, cfg = self.hparams, self.config
         L = hp['no_of_layers']
         if x.dim() != 3 or x.dtype != torch.float32 or not x.is_cuda:
@@ -574,4 +578,5 @@ class R_NETWORK(LightningModule):
                 d = self._attend(self.decoder_attention[2 * i], self.decoder_attention[2 * i + 1], y)
             if drop is not None:
                 d = drop(d)
-        return torch.sigmoid(torch.squeeze(d))
+        d = torch.squeeze(d)
+        return torch.sigmoid(d) if sigmoid else d

@@ -619,6 +619,20 @@ int dcs_bound2_apply_polar_frames_bwd(const float* Y, const float* D_raw, const 
                                       int B, int F, int Fp, int T, float eps, int hermitian, float drop_p,
                                       unsigned long long seed, const unsigned long long* seed_dev, dcs_stream_t stream);
 
+/* The real twin's step (DR-Net / DRS-Net, network_functions.py:224-232, :261-267) in the same two passes.
+ * dcs_complex_abs_f32: out[i] = |Y[i]| (hypot) for complex[n] — the network's input.
+ * dcs_rmask_apply_polar_frames_fwd: Y complex[B][F][T], D float[B][F][T] = the network's last-stage output BEFORE its sigmoid.
+ *   m = sigmoid(D), a = |y|, u = unit(y_r + eps, y_i) (the noisy phase as mag_phase_2_wave's cos / sin see it), n = a m;
+ *   out complex[(pair ? 2B : B)][T][Fp]: rows [0, B) n u, with pair != 0 rows [B, 2B) (a - n) u; bins F..Fp-1 zero.
+ *   pair == 0 is the 'dr' form (the mask is applied; no noise estimate).  M_out: optional float[B][F][T] = m.
+ * _bwd: g_D = m (1 - m) (a u.(g_n - g_s) + g_M) from the cotangent g_out of `out` (hermitian as in dcs_polar_frames_bwd;
+ *   g_s = 0 without pair) and, optionally, g_M; the forward is recomputed. */
+int dcs_complex_abs_f32(const float* Y, float* out, long n, dcs_stream_t stream);
+int dcs_rmask_apply_polar_frames_fwd(const float* Y, const float* D, float* M_out, float* out, int B, int F, int Fp, int T,
+                                     float eps, int pair, dcs_stream_t stream);
+int dcs_rmask_apply_polar_frames_bwd(const float* Y, const float* D, const float* g_out, const float* g_M, float* g_D,
+                                     int B, int F, int Fp, int T, float eps, int hermitian, int pair, dcs_stream_t stream);
+
 /* Waveform synthesis around the inverse FFT of mag_phase_2_wave / torch.istft (network_functions.py:140-150 via
  * :213-221 and :244-247).
  * dcs_polar_frames_fwd: out = |z| (cos phi + j sin phi), phi = atan2(z_i, z_r + eps), for bins f < F and zeros for
