@@ -9,11 +9,10 @@ inner ``nn.Conv2d`` / ``nn.ConvTranspose2d`` / ``nn.Linear`` modules.  The arith
 libdcsnet_hip.so; tensors cross the module boundary as complex64 ``[B,C,H,W]`` in
 channels_last memory (any input layout is accepted and converted once).
 """
-import weakref
-
 import torch
 from torch.nn import Module, Parameter, Conv2d, ConvTranspose2d, Linear
 
+from . import _derived
 from . import functional as F
 from ._lib import DcsHipError
 
@@ -79,7 +78,7 @@ class ComplexLinear(Module):
         return F.complex_linear(input, self.fc_r.weight, self.fc_i.weight, self.fc_r.bias, self.fc_i.bias)
 
 
-_EVAL_COEF = weakref.WeakKeyDictionary()      # CBN module -> (tensor refs, versions, (stats, coef)) of eval-mode calls
+_COEF = _derived.Derived()      # per CBN module: (stats, coef) of its eval-mode calls
 
 
 class _ComplexBatchNorm(Module):
@@ -161,30 +160,18 @@ class _ComplexBatchNorm(Module):
         entry (first eval pass, training mode, autograd on, parameters or running statistics changed since)."""
         if self.training or torch.is_grad_enabled() or not self.track_running_stats:
             return None
-        tensors = (self.weight, self.bias, self.running_mean, self.running_covar)
-        vers = (F.state_generation(),) + tuple(None if t is None else (t._version, t.data_ptr()) for t in tensors)
-        ent = _EVAL_COEF.get(self)
-        if ent is not None and ent[1] == vers and all((r is None and t is None) or (r is not None and r() is t)
-                                                      for r, t in zip(ent[0], tensors)):
-            return ent[2][1]
-        return None
+        cached = _COEF.peek(self, None, (self.weight, self.bias, self.running_mean, self.running_covar))
+        return None if cached is None else cached[1]
 
     def _eval_forward(self, x, rm, act, drop_p, seed):
         """Inference: the whitening + affine coefficients are constants of (weight, bias, running statistics): computed
-        by the first call, kept per module in a weak dictionary (guarded by the identity and version of the four tensors) and re-used —
-        one launch per CBN instead of two."""
-        tensors = (self.weight, self.bias, self.running_mean, self.running_covar)
-        vers = (F.state_generation(),) + tuple(None if t is None else (t._version, t.data_ptr()) for t in tensors)
-        ent = _EVAL_COEF.get(self)
-        cached = None
-        if ent is not None and ent[1] == vers and all((r is None and t is None) or (r is not None and r() is t)
-                                                      for r, t in zip(ent[0], tensors)):
-            cached = ent[2]
+        by the first call, cached per module (_derived) and re-used — one launch per CBN instead of two."""
+        sources = (self.weight, self.bias, self.running_mean, self.running_covar)
+        cached = _COEF.peek(self, None, sources)
         y, stats, coef = F.ops.cbn(x, self.weight, self.bias, rm, self.running_covar, self.eps, -1.0, False, act,
                                    drop_p, seed, coef_cached=cached)
-        if cached is None and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
-            refs = tuple(None if t is None else weakref.ref(t) for t in tensors)
-            _EVAL_COEF[self] = (refs, vers, (stats, coef))
+        if cached is None:
+            _COEF.put(self, None, sources, (stats, coef))
         return y
 
 

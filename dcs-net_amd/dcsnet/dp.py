@@ -267,7 +267,7 @@ class TrainStep:
             from . import ops
             self.seed_state = torch.zeros(1, dtype=torch.int64, device=self.bucket.flat.device)
             ops.SEED_STATE = self.seed_state
-        self._graph = self._graph_opt = self._static_batch = self._static_loss = None
+        self._graph = self._graph_opt = self._static_batch = self._static_loss = self._keep = None
         # The pack plan replays every weight re-layout recorded during the first step from the recorded SOURCE POINTERS: safe only
         # for a network all of whose packs read registered parameters (stable addresses in the flat bucket) through
         # functional.packed_weight (destinations kept alive by the plan) — C_NETWORK says so (pack_plan_safe).  R_NETWORK derives its
@@ -445,7 +445,7 @@ class TrainStep:
         return loss
 
     def _capture(self, batch):
-        from . import functional
+        from . import _derived, functional
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         functional.bump_param_generation()                 # packed weights must be re-made INSIDE the graph
         # (noise, clean, noisy) in ONE allocation: the step synthesises the two target waveforms as a single batch of 2B
@@ -460,9 +460,12 @@ class TrainStep:
         static = (*self._static_batch, *batch[3:])
         g = torch.cuda.CUDAGraph()
         # thread_local: a collective backend's watchdog thread may touch the HIP runtime while this thread captures
-        with torch.cuda.graph(g, capture_error_mode='thread_local'):
+        # On purpose, as every graph owner does: the graph reads the cached window and envelope the warm-up steps left, and
+        # the cache may evict them.  collect() holds what the cache SERVED during the capture, which is those two: the
+        # step's packs come from the pack plan, not through the cache.
+        with _derived.collect() as self._keep, torch.cuda.graph(g, capture_error_mode='thread_local'):
             loss = self._device_step(static, world)
-        functional.bump_param_generation()                 # cache entries made during capture live in its pool
+        functional.bump_param_generation()                 # the capture recorded, nothing ran: the pack plan's packs were not re-made
         self._graph, self._static_loss, self._graph_world = g, loss.detach(), world
         self._graph_opt = None
         self._graph_counters = self._counted() if world > 1 else None      # (world 1: the captured optimizer half took them)

@@ -19,15 +19,16 @@ kernel writes the static input, (2) net(Y, bound=False) runs in eval() under no_
 path makes both estimates; then ONE stitch launch cross-fades all segment waveforms into the recordings.  With use_graph the
 steps 1-3 are captured once and replayed per batch; the replays read the batch's rows of the table from the same device tensor.
 
-Lifetime of what a captured graph reads.  A graph holds addresses, not references.  The Enhancer therefore keeps its own
-references to the device window and the inverse envelope the capture baked in (network_functions._windows / _envelopes evict
-at 64 entries and would free them under a live graph), to the packed weights and inference constants the warm-up passes left
-in the package's caches, and to its store, table and output buffers; and it captures again whenever the network's state or
-one of those buffers changes.
+Lifetime of what a captured graph reads.  A graph holds addresses, not references, and the package's cache of derived
+tensors (_derived: packed weights, inference constants, windows) may evict any entry.  The one rule: whoever captures keeps
+what its graph reads.  The Enhancer owns its window, inverse envelope, store, table and output buffers; its last warm-up
+pass runs inside _derived.collect(), which hands it a reference to every cached value that pass was served; and it captures
+again whenever the network's state or one of those buffers changes.
 """
 import numpy as np
 import torch
 
+from . import _derived
 from . import functional as F
 from . import ops
 from ._lib import DcsHipError
@@ -196,17 +197,18 @@ class Enhancer:
                 self._offsets.data_ptr(), tuple((id(t), t._version, t.data_ptr()) for t in tensors))
 
     def _step_fn(self):
-        """The per-batch callable -> static or fresh waveforms.  Captured once per state (two eager warm-ups first, which also
-        fill the package's caches of packed weights and inference constants the graph will read)."""
+        """The per-batch callable -> static or fresh waveforms.  Captured once per state (two eager warm-ups first: the first
+        fills the cache of packed weights and inference constants, the second is served from it exactly what the graph will read)."""
         if not self.use_graph:
             return self._run_batch
         key = self._state_key()
         if self._graph is None or key != self._graph_key:
             self._graph = self._graph_out = None
-            for _ in range(2):
+            self._run_batch()
+            with _derived.collect() as kept:
                 self._run_batch()
             torch.cuda.synchronize(self.device)
-            self._keep = self._cached_operands()
+            self._keep = kept
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 out = self._run_batch()
@@ -216,15 +218,6 @@ class Enhancer:
             self._graph.replay()
             return self._graph_out
         return replay
-
-    def _cached_operands(self):
-        """References, not copies, to what the warm-up passes left in the package's caches: the graph reads these allocations,
-        the caches that own them may drop them."""
-        from . import complexLayers
-        mods = list(self.net.modules())
-        return (list(F._pack_cache.values()),
-                [complexLayers._EVAL_COEF.get(m) for m in mods if isinstance(m, complexLayers.ComplexBatchNorm2d)],
-                [dict(F._LSTM_EVAL_OPERANDS.get(m, {})) for m in mods if isinstance(m, torch.nn.LSTM)])
 
     # ---- public --------------------------------------------------------------------------------------------------------
 
@@ -320,7 +313,3 @@ class MagnitudeEnhancer(Enhancer):
         d_raw = self.net(ops.complex_abs(Y), sigmoid=False).reshape(Y.shape)       # (forward squeezes a batch of one)
         return F.rmask_apply_polar_wave(Y, d_raw, self.window, self.inv_env, 512, self.hop, self.synth_scale, self.eps,
                                         pair=self.mode == 'drs', want_mask=False)[1]
-
-    def _cached_operands(self):
-        from . import r_network
-        return (list(F._pack_cache.values()), [e[2] for e in r_network._PACKS.values()])

@@ -9,39 +9,36 @@ import weakref
 
 import torch
 
+from . import _derived
 from . import ops
 from .ops import ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID, to_nhwc, from_nhwc  # noqa: F401
 from ._lib import DcsHipError
 
-_pack_cache = {}
-
-
-_param_generation = 0
+_PACKED = _derived.Derived(capacity=512)         # packed_weight(): per weight tensor and pack flags
 
 
 def bump_param_generation():
     """Called by optimizers that update parameters outside torch's version counters (the fused
     HIP Adam, a replayed train-step graph): every packed weight and every inference-time constant derived from
-    parameters or running statistics becomes stale."""
-    global _param_generation
-    _param_generation += 1
-    _pack_cache.clear()
+    parameters or running statistics becomes stale (and is re-made by its next lookup)."""
+    _derived.bump_generation()
     ops.pack_plan_invalidate()
 
 
 def note_state_update():
-    """A kernel changed module state behind torch's version counters (train-mode CBN: running statistics)."""
-    global _param_generation
-    _param_generation += 1
+    """A kernel changed module state behind torch's version counters (train-mode CBN: running statistics).  The one stamp
+    makes every state-tracking entry stale, packed weights included: an eval network served next to a train-mode pass
+    re-packs after each such pass (the train step's own packs come from its pack plan, in front of the cache)."""
+    _derived.bump_generation()
 
 
-def state_generation():
-    return _param_generation
+state_generation = _derived.generation
 
 
 def begin_pack_plan():
-    """Start recording every weight pack of the coming step (they still execute)."""
-    _pack_cache.clear()
+    """Start recording every weight pack of the coming step (they still execute: the generation bump makes every cached
+    pack stale, so each lookup of the step packs and records)."""
+    _derived.bump_generation()
     return ops.pack_plan_begin()
 
 
@@ -55,13 +52,9 @@ def run_pack_plan(plan):
     ops.pack_plan_run(plan)
 
 
-def _ver(t):
-    return (0, 0) if t is None else (id(t), t._version)
-
-
 def packed_weight(w_r, w_i, b_r, b_i, transposed, up=(1, 1), tap_rows=0):
-    """Packed (wp, bias) for a weight pair; cached per tensor OBJECT and version (the weakrefs
-    guard against a recycled id()).  1x1 / Linear weights may be passed 2-D.  `up`: upsample factors
+    """Packed (wp, bias) for a weight pair, cached (_derived) per weight tensor and pack flags; the panel layout depends on the
+    conv precision.  1x1 / Linear weights may be passed 2-D.  `up`: upsample factors
     of the conv call the weight is for.  tap_rows = ct > 0: the 1x1 "tap channel" weight of the tap-sum factorisation
     instead (ops.pack_tap_rows)."""
     plan = ops.PLAN
@@ -73,25 +66,21 @@ def packed_weight(w_r, w_i, b_r, b_i, transposed, up=(1, 1), tap_rows=0):
                     w_r._version, w_i._version, None if b_r is None else b_r._version,
                     None if b_i is None else b_i._version):
                 return e[1]
-    key = (_ver(w_r), _ver(w_i), _ver(b_r), _ver(b_i), bool(transposed), tuple(up), int(tap_rows))
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0]() is w_r and hit[1]() is w_i:
-        return hit[2]
-    if len(_pack_cache) > 512:
-        _pack_cache.clear()
-    d = lambda t: None if t is None else t.detach()
-    wr, wi = d(w_r), d(w_i)
-    if wr.dim() == 2:
-        wr, wi = wr.view(*wr.shape, 1, 1), wi.view(*wi.shape, 1, 1)
-    if tap_rows:
-        packed = ops.pack_tap_rows(wr, wi, int(tap_rows))
-    else:
-        packed = ops.pack_conv_weight(wr, wi, d(b_r), d(b_i), transposed, tuple(up))
-    _pack_cache[key] = (weakref.ref(w_r), weakref.ref(w_i), packed)
-    if plan is not None and plan.recording:
-        wref = lambda t: None if t is None else weakref.ref(t)
-        plan.fwd[pkey] = [(wref(w_r), wref(w_i), wref(b_r), wref(b_i)), packed, None]
-    return packed
+
+    def make():
+        d = lambda t: None if t is None else t.detach()
+        wr, wi = d(w_r), d(w_i)
+        if wr.dim() == 2:
+            wr, wi = wr.view(*wr.shape, 1, 1), wi.view(*wi.shape, 1, 1)
+        if tap_rows:
+            packed = ops.pack_tap_rows(wr, wi, int(tap_rows))
+        else:
+            packed = ops.pack_conv_weight(wr, wi, d(b_r), d(b_i), transposed, tuple(up))
+        if plan is not None and plan.recording:
+            wref = lambda t: None if t is None else weakref.ref(t)
+            plan.fwd[pkey] = [(wref(w_r), wref(w_i), wref(b_r), wref(b_i)), packed, None]
+        return packed
+    return _PACKED.get(w_r, (bool(transposed), tuple(up), int(tap_rows)), (w_r, w_i, b_r, b_i), make, ops.conv_precision())
 
 
 ATTENTION_BATCH_MAX = ops.ATTENTION_BATCH_MAX
@@ -762,31 +751,25 @@ def _stacked_lstm(real_lstm):
     return st
 
 
-_LSTM_EVAL_OPERANDS = weakref.WeakKeyDictionary()      # real nn.LSTM -> {layer: (key, parameter refs, stacks)}
+_LSTM_OPERANDS = _derived.Derived()         # per real nn.LSTM and layer: the stacked inference operands
 
 
 def _lstm_layer_operands(sets, layer):
     """Stacked (w_ih [2, 8H, in], bias [2, 8H], w_hh [2, 2, 4H, H]) of one layer of both nn.LSTM containers.  Without
-    autograd (inference) the stacks are cached per parameter identity + version: re-making them costs ~12 cat / add
-    launches per layer and pass."""
+    autograd (inference) the stacks are cached (_derived): re-making them costs ~12 cat / add launches per layer and pass."""
     names = [f'_l{layer}', f'_l{layer}_reverse']
     params = [getattr(m, k + n) for m in sets for n in names for k in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')]
+
+    def make():
+        w_ih = torch.stack([torch.cat([getattr(m, 'weight_ih' + n) for n in names]) for m in sets])      # [2, 8H, in]
+        bias = torch.stack([torch.cat([getattr(m, 'bias_ih' + n) + getattr(m, 'bias_hh' + n) for n in names])
+                            for m in sets])                                                                # [2, 8H]
+        w_hh = torch.stack([torch.stack([getattr(m, 'weight_hh' + n) for n in names]) for m in sets]).contiguous()   # [2,2,4H,H]
+        return w_ih, bias, w_hh
     cacheable = not (torch.is_grad_enabled() and any(p.requires_grad for p in params))
-    if cacheable:
-        key = (_param_generation, tuple((p.data_ptr(), p._version) for p in params))
-        hit = _LSTM_EVAL_OPERANDS.get(sets[0], {}).get(layer)
-        if hit is not None and hit[0] == key and all(r() is p for r, p in zip(hit[1], params)):
-            return hit[2]
-    w_ih = torch.stack([torch.cat([getattr(m, 'weight_ih' + n) for n in names]) for m in sets])      # [2, 8H, in]
-    bias = torch.stack([torch.cat([getattr(m, 'bias_ih' + n) + getattr(m, 'bias_hh' + n) for n in names])
-                        for m in sets])                                                                # [2, 8H]
-    w_hh = torch.stack([torch.stack([getattr(m, 'weight_hh' + n) for n in names]) for m in sets]).contiguous()   # [2,2,4H,H]
-    if cacheable:
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            return w_ih, bias, w_hh             # tensors made during capture live in the graph's pool: do not keep them
-        _LSTM_EVAL_OPERANDS.setdefault(sets[0], {})[layer] = (
-            key, tuple(weakref.ref(p) for p in params), (w_ih.detach(), bias.detach(), w_hh.detach()))
-    return w_ih, bias, w_hh
+    if not cacheable:
+        return make()
+    return _LSTM_OPERANDS.get(sets[0], layer, params, lambda: tuple(t.detach() for t in make()))
 
 
 def complex_lstm(z, real_lstm, imag_lstm):

@@ -14,6 +14,7 @@ import sys
 
 import torch
 
+from . import _derived
 from . import functional as F
 from . import metrics as _metrics
 from . import ops
@@ -145,45 +146,22 @@ class ComplexAdaptiveMaxPool2d(torch.nn.Module):
 
 # ---- step functions (plumbing on PyTorch-ROCm around the HIP path) ------------------------------
 
-_windows = {}
+_WINDOWS = _derived.Derived(capacity=64, tracks_state=False)
+_ENVELOPES = _derived.Derived(capacity=64, tracks_state=False)
 
 
 def _window_on(config, device):
     """The synthesis window on `device`, uploaded once per window TENSOR (a per-call host-to-device copy would also be illegal
-    inside a hipGraph capture).  The entry holds a weak reference to the host tensor: a recycled id() of a dead window must not
-    serve another config the old one's copy."""
-    import weakref
+    inside a hipGraph capture); cached (_derived) with the host tensor as owner."""
     src = config.window
     if src.device == device:
         return src
-    key = (id(src), device)
-    ent = _windows.get(key)
-    if ent is not None and ent[0]() is src and ent[2] == src._version:
-        return ent[1]
-    w = src.to(device)
-    if not (device.type == 'cuda' and torch.cuda.is_current_stream_capturing()):
-        if len(_windows) > 64:
-            _windows.clear()
-        _windows[key] = (weakref.ref(src), w, src._version)
-    return w
-
-
-_envelopes = {}
+    return _WINDOWS.get(src, device, (src,), lambda: src.to(device))
 
 
 def _inv_envelope(window, T, hop):
-    """1 / squared-window envelope for T frames; depends only on (window, T, hop): computed once per device window tensor (HIP).
-    The entry keeps the window alive, so its address cannot be handed to another tensor while the entry exists."""
-    key = (window.data_ptr(), T, hop, window.device)
-    ent = _envelopes.get(key)
-    if ent is not None and ent[0] is window and ent[2] == window._version:
-        return ent[1]
-    env = ops.istft_envelope(window, T, hop)
-    if not (window.is_cuda and torch.cuda.is_current_stream_capturing()):
-        if len(_envelopes) > 64:
-            _envelopes.clear()
-        _envelopes[key] = (window, env, window._version)
-    return env
+    """1 / squared-window envelope for T frames; depends only on (window, T, hop): computed once per device window tensor (HIP)."""
+    return _ENVELOPES.get(window, (T, hop), (window,), lambda: ops.istft_envelope(window, T, hop))
 
 
 def _frames_to_wave(comp_t, n_fft, hop, window, normalized):

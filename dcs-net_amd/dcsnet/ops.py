@@ -52,17 +52,16 @@ def set_conv_precision(mode):
     """'bf16x6' (default: fp32 emulated on the bf16 MFMA — exact three-way bf16 splits of both operands, the six leading
     cross products accumulated in fp32; product error < 2^-24, measured error against fp64 below the native
     instruction's), 'f32' (native fp32 MFMA) or 'bf16' (bf16-rounded operands, fp32 accumulate: BASELINE configs[4]) in
-    the MFMA conv forward / data gradient (dcs_set_conv_precision).  Every packed weight made under the other mode becomes invalid: the caches
-    are cleared here, a recorded pack plan must be re-recorded by its owner."""
+    the MFMA conv forward / data gradient (dcs_set_conv_precision).  Every packed weight made under the other mode becomes invalid: the
+    precision is part of every cached pack's stamp (_derived), a recorded pack plan must be re-recorded by its owner."""
     code = {'f32': 0, 'fp32': 0, 'bf16': 1, 'bf16x6': 2}[mode]
     check(_lib.load().dcs_set_conv_precision(code), 'dcs_set_conv_precision')
-    global BF16_OPERANDS_ON_PURPOSE
+    global BF16_OPERANDS_ON_PURPOSE, _conv_precision
+    _conv_precision = _CONV_PRECISIONS[code]
     if code != 1:
         BF16_OPERANDS_ON_PURPOSE = False                       # a switch away from 'bf16' ends the choice
     elif not _IN_SET_ACTIVATION_DTYPE:
         BF16_OPERANDS_ON_PURPOSE = True                        # chosen by the caller; a later set_activation_dtype('bf16') keeps it
-    from . import functional
-    functional._pack_cache.clear()
     pack_plan_drop()
 
 
@@ -73,8 +72,15 @@ BF16_OPERANDS_ON_PURPOSE = _os.environ.get('DCS_CONV_PRECISION', '').strip() == 
 _IN_SET_ACTIVATION_DTYPE = False
 
 
+_CONV_PRECISIONS = ('f32', 'bf16', 'bf16x6')
+_conv_precision = None       # the library's mode: read from it once (its preset), then kept by set_conv_precision, its only writer
+
+
 def conv_precision():
-    return ('f32', 'bf16', 'bf16x6')[_lib.load().dcs_get_conv_precision()]
+    global _conv_precision
+    if _conv_precision is None:
+        _conv_precision = _CONV_PRECISIONS[_lib.load().dcs_get_conv_precision()]
+    return _conv_precision
 
 
 class PackPlan:

@@ -43,6 +43,7 @@ hparams['dropout'] (:152) while dropout_conv is not; torch.squeeze drops the bat
 import os
 import torch
 
+from . import _derived
 from . import ops
 from . import functional as F
 from ._lib import DcsHipError
@@ -84,23 +85,13 @@ class RealSpatialAttention(torch.nn.Module):          # r_network.py:29-42
         return sa[..., 0]                                                                 # real part: [B,H,W,1]
 
 
-_PACKS = {}
+_PACKED = _derived.Derived(capacity=512)
 
 
 def _packed(owner, tag, tensors, make):
-    """Inference-time constant derived from parameters: cached per (module, tag), guarded by tensor identity/version and
-    the global state generation (functional.state_generation: bumped by anything that rewrites parameters in place)."""
-    key = (F.state_generation(), tuple((id(t), t.data_ptr(), t._version) for t in tensors))
-    ent = _PACKS.get((id(owner), tag))
-    if ent is not None and ent[0] == key and ent[1]() is owner:
-        return ent[2]
-    import weakref
-    val = make()
-    if not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
-        if len(_PACKS) > 512:
-            _PACKS.clear()
-        _PACKS[(id(owner), tag)] = (key, weakref.ref(owner), val)
-    return val
+    """Inference-time constant derived from parameters, cached (_derived) per (module, tag); the conv precision decides the
+    layout of the panels ops.pack_conv_weight makes."""
+    return _PACKED.get(owner, tag, tensors, make, ops.conv_precision())
 
 
 _CONJ = {}
@@ -113,7 +104,7 @@ def _conj_vec(device):
     if v is None:
         v = torch.ones(2, dtype=torch.float32, device=device)
         v[1].fill_(-1.0)
-        if not (device.type == 'cuda' and torch.cuda.is_current_stream_capturing()):
+        if not _derived.capturing():
             _CONJ[device] = v
     return v
 

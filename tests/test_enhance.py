@@ -240,14 +240,20 @@ def test_a_recording_does_not_depend_on_its_batch_neighbours(dev, waves16, wave4
 
 
 def test_replay_after_the_envelope_and_window_caches_evicted(dev, waves16, captured):
-    from dcsnet import network_functions as nf
+    """The captured graph reads the Enhancer's own window and envelope and the cached values _derived.collect() handed it:
+    pushing the envelope and the pack caches past their capacities (64, 512) takes nothing from under it."""
+    from dcsnet import network_functions as nf, functional as F
     enh, plan, tables, noise, speech = captured
     assert enh._graph is not None
     graph = enh._graph
     window = torch.hann_window(512).to(dev)
     for t in range(70):
         nf._inv_envelope(window, 16 + 8 * t, HOP)
-    assert len(nf._envelopes) <= 65
+    assert len(nf._ENVELOPES) <= 64
+    pairs = [(torch.full((2, 2, 1, 1), 1.0 + i, device=dev), torch.ones(2, 2, 1, 1, device=dev)) for i in range(520)]
+    for w_r, w_i in pairs:                                               # (alive: an entry goes with its owner)
+        F.packed_weight(w_r, w_i, None, None, False)
+    assert len(F._PACKED) == 512
     _, _, noise2, speech2 = enh.enhance_segments(waves16, 16000)
     assert enh._graph is graph                                           # replayed, not captured again
     assert torch.equal(noise2, noise) and torch.equal(speech2, speech)

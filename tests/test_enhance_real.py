@@ -130,6 +130,26 @@ def test_a_recording_does_not_depend_on_its_batch_neighbours(dev, waves16, captu
         assert float(among[i].abs().max()) > 1e-3
 
 
+def test_replay_after_the_envelope_and_pack_caches_evicted(dev, waves16, captured):
+    """tests/test_enhance.py's test of the same name for the real twin: the envelope cache and the real network's pack cache
+    pushed past their capacities (64, 512) take nothing from under the captured graph."""
+    from dcsnet import network_functions as nf, r_network
+    enh, plan, tables, noise, speech = captured
+    assert enh._graph is not None
+    graph = enh._graph
+    window = torch.hann_window(512).to(dev)
+    for t in range(70):
+        nf._inv_envelope(window, 16 + 8 * t, HOP)
+    assert len(nf._ENVELOPES) <= 64
+    owner, w = torch.nn.Identity(), torch.ones(2, 2, 1, 1, device=dev)
+    for tag in range(520):
+        r_network._packed(owner, tag, (w,), lambda: w * float(tag))
+    assert len(r_network._PACKED) == 512
+    _, _, noise2, speech2 = enh.enhance_segments(waves16, 16000)
+    assert enh._graph is graph                                           # replayed, not captured again
+    assert torch.equal(noise2, noise) and torch.equal(speech2, speech)
+
+
 def _reference_fp64(x, plan, i):
     """Recording i through the reference's own chain in fp64 on the CPU, segment by segment: torch.stft of the zero-extended
     recording (centred, reflected at 0 and at L_i), bins 1..256, oracle.nf_oracle.mag_phase_2_wave of the noisy magnitude on the
