@@ -370,7 +370,7 @@ def test_attention_blocks_batched(dev):
 
 # --------------------------------------------------------------------------------- LSTM, mask
 
-@pytest.mark.parametrize('B,S', [(2, 8), (3, 40), (1, 1)])
+@pytest.mark.parametrize('B,S', [(2, 8), (3, 40), (1, 1), (2, 2), (2, 3)])
 def test_complex_lstm_backward(dev, B, S):
     from dcsnet.c_network import ComplexLSTM
     torch.manual_seed(B * 10 + S)

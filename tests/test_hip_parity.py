@@ -244,7 +244,7 @@ def test_complex_linear(dev):
     close(y, m(z))
 
 
-@pytest.mark.parametrize('B,S', [(2, 8), (3, 64), (1, 1)])
+@pytest.mark.parametrize('B,S', [(2, 8), (3, 64), (1, 1), (2, 2), (2, 3)])
 def test_complex_lstm_persistent_kernel(dev, B, S):
     from dcsnet.c_network import ComplexLSTM
     torch.manual_seed(B * 100 + S)
