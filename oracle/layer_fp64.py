@@ -444,3 +444,146 @@ def lstm_reference(state, z, g_out, wide):
     y = m(zz)
     (torch.view_as_real(y) * torch.view_as_real(g_out.to(cd))).sum().backward()
     return dict(y=y.detach(), gz=zz.grad, grads={n: q.grad for n, q in m.named_parameters()})
+
+
+# ---- the folded inference epilogue: conv -> eval-mode CBN -> activation as one kernel (tests/test_infer_epilogue.py) ----
+
+ACT_NAMES = ('none', 'relu', 'lrelu', 'sigmoid')
+_POST_EVAL = dict(_POST, sigmoid=nf.complex_sigmoid)
+CROSS_MIN = 0.25              # min(|q1|, |q2|) >= CROSS_MIN * max(|q0|, |q3|) in every channel of a non-hard state
+
+
+def eval_cbn_state(C, seed, hard=False):
+    """Seeded eval-mode CBN tensors whose folded coefficients have LARGE cross terms: dict(weight [C,3] = (W_rr, W_ii, W_ri),
+    bias [C,2], running_mean float [C,2], running_covar [C,3] = (V_rr, V_ii, V_ri)).
+
+    V_rr, V_ii ~ U[0.5, 2]; V_ri = rho sqrt(V_rr V_ii), rho = s U[0.5, 0.9] with a random sign s per channel (hard: |rho| in
+    [0.99, 0.999], a nearly singular covariance); W_rr, W_ii = sqrt(2) + U[-0.3, 0.3]; W_ri = -s U[0.4, 0.9]: the whitening
+    matrix's cross term R_ri has the sign of -V_ri, so the weight's cross term adds to it instead of cancelling it.  Mean
+    components U[-2, 2], bias U[-0.5, 0.5].  (seeded_state.fill_state has |V_ri|, |W_ri| <= 0.3: q1, q2 a fraction of q0, q3.)"""
+    g = torch.Generator().manual_seed(seed)
+    u = lambda lo, hi, *s: torch.rand(*s, generator=g) * (hi - lo) + lo
+    vrr, vii = u(0.5, 2.0, C), u(0.5, 2.0, C)
+    s = torch.where(torch.rand(C, generator=g) < 0.5, -torch.ones(C), torch.ones(C))
+    rho = s * (u(0.99, 0.999, C) if hard else u(0.5, 0.9, C))
+    vri = rho * torch.sqrt(vrr * vii)
+    weight = torch.stack((math.sqrt(2.0) + u(-0.3, 0.3, C), math.sqrt(2.0) + u(-0.3, 0.3, C), -s * u(0.4, 0.9, C)), dim=1)
+    return dict(weight=weight, bias=u(-0.5, 0.5, C, 2), running_mean=u(-2.0, 2.0, C, 2),
+                running_covar=torch.stack((vrr, vii, vri), dim=1))
+
+
+def eval_coef_reference(state, eps=1e-5, wide=True):
+    """[C, 6] = (q0, q1, q2, q3, q4, q5) of re' = q0 re + q1 im + q4, im' = q2 re + q3 im + q5: complexPyTorch's eval-mode
+    whitening (the closed-form inverse square root of the 2 x 2 covariance) followed by the affine map, evaluated in fp64
+    (wide) or fp32."""
+    dt = torch.float64 if wide else torch.float32
+    w, b, m, v = (state[n].to(dt) for n in ('weight', 'bias', 'running_mean', 'running_covar'))
+    crr, cii, cri = v[:, 0] + eps, v[:, 1] + eps, v[:, 2]
+    s = torch.sqrt(crr * cii - cri * cri)
+    t = torch.sqrt(cii + crr + 2 * s)
+    ist = 1.0 / (s * t)
+    rrr, rii, rri = (cii + s) * ist, (crr + s) * ist, -cri * ist
+    q0, q1 = w[:, 0] * rrr + w[:, 2] * rri, w[:, 0] * rri + w[:, 2] * rii
+    q2, q3 = w[:, 2] * rrr + w[:, 1] * rri, w[:, 2] * rri + w[:, 1] * rii
+    return torch.stack((q0, q1, q2, q3, b[:, 0] - q0 * m[:, 0] - q1 * m[:, 1], b[:, 1] - q2 * m[:, 0] - q3 * m[:, 1]), dim=1)
+
+
+def cross_ratio(coef):
+    """min over channels of min(|q1|, |q2|) / max(|q0|, |q3|)."""
+    q = coef.double().abs()
+    return float((torch.minimum(q[:, 1], q[:, 2]) / torch.maximum(q[:, 0], q[:, 3])).min())
+
+
+def apply_coef(pre, coef, act='none'):
+    """act(A pre + c) on a complex [B,C,H,W] tensor with coef [C,6], in coef's real dtype."""
+    q = coef[None, :, :, None, None]
+    re, im = pre.real.to(coef.dtype), pre.imag.to(coef.dtype)
+    z = torch.complex(q[:, :, 0] * re + q[:, :, 1] * im + q[:, :, 4], q[:, :, 2] * re + q[:, :, 3] * im + q[:, :, 5])
+    with cdtype(z.dtype):
+        return _POST_EVAL[act](z)
+
+
+def eval_cbn_module(state, eps, wide):
+    """cpt.ComplexBatchNorm2d in .eval() holding `state`."""
+    C = state['weight'].shape[0]
+    mod = cpt.ComplexBatchNorm2d(C, eps=eps)
+    with torch.no_grad():
+        mod.weight.copy_(state['weight']); mod.bias.copy_(state['bias'])
+        mod.running_covar.copy_(state['running_covar'])
+    if wide:
+        mod = mod.double()
+    mod.running_mean = torch.view_as_complex(state['running_mean'].to(torch.float64 if wide else torch.float32).contiguous())
+    return mod.eval()
+
+
+def folded_reference(L, case, state, act, wide, eps=1e-5, pre=None):
+    """The oracle's own modules on the case's operands: conv_module -> ComplexBatchNorm2d.eval() holding `state` ->
+    complex_relu / complex_lrelu / complex_sigmoid, in fp64 (wide) or fp32.  dict(y, pre): the output and the raw conv
+    output the CBN read, complex [B, Cout, Hout, Wout].  pre: the conv output of an earlier call with the same operands and
+    width (another activation of the same row)."""
+    cd = torch.complex128 if wide else torch.complex64
+    with cdtype(cd), torch.no_grad():
+        if pre is None:
+            m, _, _ = conv_module(L, case, wide)
+            z = case['x'].to(cd)
+            if tuple(L.up) != (1, 1):
+                z = cpt.complex_upsample(z, scale_factor=tuple(L.up), mode='nearest')
+            pre = m(z)
+        assert pre.dtype == cd
+        y = _POST_EVAL[act](eval_cbn_module(state, eps, wide)(pre))
+    return dict(y=y, pre=pre)
+
+
+def live_branches(y, act):
+    """(share of real output components on the upper branch of the activation, on the lower one): > 0 / <= 0 after ReLU
+    (the clamped ones), > 0 / < 0 after the leaky ReLU, above / below 1/2 after the sigmoid."""
+    v = torch.view_as_real(y).double()
+    t = 0.5 if act == 'sigmoid' else 0.0
+    return float((v > t).double().mean()), float((v <= t).double().mean())
+
+
+EPILOGUE_FAULTS = ('q1_im_dropped', 'q2_re_dropped', 'q1_q2_swapped', 'additive_dropped', 'neighbour_channel_coef', 'activation_skipped')
+
+
+def epilogue_faults(y_ref, coef, pre, act='relu', n=16):
+    """{fault: y}: the fp64 reference rounded to fp32 with one epilogue fault each in `n` elements of ONE output row (the
+    last sample's middle row: all columns and channels of it) — the references the comparator has to refuse.
+
+      q1_im_dropped / q2_re_dropped   the cross term of the real / imaginary part left out
+      q1_q2_swapped                   the two cross coefficients exchanged
+      additive_dropped                q4, q5 left out
+      neighbour_channel_coef          channel c evaluated with channel c ^ 1's coefficients (the pairing of the kernels that
+                                      keep two channels per thread)
+      activation_skipped              A pre + c stored as it is
+
+    The elements are the first n (in (column, channel) order) of those whose output changes by at least the median of the
+    non-zero changes in that row: never one where im ~ 0 or where the ReLU hides the fault."""
+    coef = coef.double()
+    q = {name: coef.clone() for name in EPILOGUE_FAULTS}
+    q['q1_im_dropped'][:, 1] = 0
+    q['q2_re_dropped'][:, 2] = 0
+    q['q1_q2_swapped'][:, 1], q['q1_q2_swapped'][:, 2] = coef[:, 2], coef[:, 1]
+    q['additive_dropped'][:, 4:] = 0
+    C = coef.shape[0]
+    if C > 1:
+        q['neighbour_channel_coef'] = coef[torch.arange(C) ^ 1 if C % 2 == 0 else torch.arange(C).roll(1)]
+    else:
+        del q['neighbour_channel_coef']            # one channel has no neighbour
+    b, h = y_ref.shape[0] - 1, y_ref.shape[2] // 2
+    row = pre[b:b + 1, :, h:h + 1].to(torch.complex128)
+    good = y_ref[b, :, h].to(torch.complex128)
+    out = {}
+    for name, qq in q.items():
+        if name == 'activation_skipped' and act == 'none':
+            continue
+        bad = apply_coef(row, qq, 'none' if name == 'activation_skipped' else act)[0, :, 0]        # [C, W]
+        change = (bad - good).abs().t()                                                               # [W, C]
+        live = change[change > 0]
+        assert live.numel() >= n, f'{name}: the fault changes {live.numel()} elements of the row'
+        pick = (change >= live.median()).flatten().nonzero().flatten()[:n]
+        y = y_ref.to(torch.complex64).clone()
+        for i in pick.tolist():
+            w_, c_ = divmod(i, C)
+            y[b, c_, h, w_] = bad[c_, w_].to(torch.complex64)
+        out[name] = y
+    return out

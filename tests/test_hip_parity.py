@@ -952,6 +952,33 @@ def test_folded_cbn_epilogue_under_co_resident_bf16_mfma_workgroups(dev):
     for a in out['bf16x6']:
         assert torch.equal(a, out['bf16x6'][0])                       # run-to-run identical
         assert float((a - out['f32'][0]).abs().max()) <= 2e-5 * scale
+    # Two modes of one kernel agree also where both lack a term, so the same launches are held to references as well, with a
+    # CBN state whose cross coefficients are as large as the diagonal ones (oracle/layer_fp64.eval_cbn_state; randn coefficients
+    # have no CBN behind them): in each mode the folded launch — three times — equals conv + ops.cbn (cbn_apply_kernel, a VALU
+    # kernel of its own) bit for bit, every element, and sample 0 of it the oracle modules in fp64 under the per-op rule
+    # (tests/test_infer_epilogue.py, tiers C and A).
+    from oracle import layer_fp64 as L64, rnet_layer_fp64 as R64
+    state = L64.eval_cbn_state(C, 9)
+    assert L64.cross_ratio(L64.eval_coef_reference(state, 1e-5, True)) >= L64.CROSS_MIN
+    L = L64.ConvLayer('enc5', H, W, C, 0, C, k, st, (1, 1), False)
+    case = dict(x=back(x[:1]), w_r=w_r.cpu(), w_i=w_i.cpu(), b_r=b_r.cpu(), b_i=b_i.cpu())
+    threads = L64.set_threads()
+    ref, ref32 = (L64.folded_reference(L, case, state, 'relu', wide)['y'] for wide in (True, False))
+    torch.set_num_threads(threads)
+    bn = tuple(state[n].to(dev).contiguous() for n in ('weight', 'bias', 'running_mean', 'running_covar'))
+    try:
+        for mode in ('f32', 'bf16x6'):
+            ops.set_conv_precision(mode)
+            wp, bias = ops.pack_conv_weight(w_r, w_i, b_r, b_i, False, (1, 1))
+            raw = ops.cconv2d(x, None, wp, bias, (k, k), st, (1, 1), (1, 1), F.ACT_NONE)
+            two, _, coef_bn = ops.cbn(raw, *bn, 1e-5, -1.0, False, F.ACT_RELU)
+            for _ in range(3):
+                y = ops.cconv2d(x, None, wp, bias, (k, k), st, (1, 1), (1, 1), F.ACT_RELU, coef=coef_bn)
+                assert torch.equal(y, two), (mode, int((y != two).sum()))
+            rows, misses = R64.compare(dict(y=back(y[:1])), dict(y=ref), dict(y=ref32))
+            assert not misses, (mode, rows)
+    finally:
+        ops.set_conv_precision(default)
 
 
 def test_double_bound_mask_application_in_one_kernel(dev):
