@@ -35,6 +35,24 @@ from ._lib import DcsHipError
 from .audio_store import _as_float32, _signal_shape
 
 
+def read_pcm16(paths, rate0=None):
+    """Mono 16-bit PCM WAV files of one sample rate (scipy.io.wavfile) -> (list of int16 arrays, the rate).  rate0: the rate
+    of files read before these."""
+    from scipy.io import wavfile
+    waves = []
+    for p in paths:
+        rate, data = wavfile.read(p)
+        if data.dtype != np.int16:
+            raise ValueError(f'{p}: {data.dtype} samples; only 16-bit PCM WAV is decoded')
+        if data.ndim != 1:
+            raise ValueError(f'{p}: {data.shape[1]} channels; only mono WAV is read')
+        if rate0 is not None and rate != rate0:
+            raise ValueError(f'{p}: {rate} Hz, the files before it {rate0} Hz; one sample rate per call')
+        rate0 = rate
+        waves.append(data)
+    return waves, rate0
+
+
 class SegmentPlan:
     """Host-side geometry of one call (integers only).  lengths[i]: samples of recording i at config.sr; n_seg[i] its
     segments; frames[i] = Tp_i, the frames of the zero-extended recording; item / first_frame: the segment table, padded with
@@ -136,7 +154,13 @@ class Enhancer:
             cap_n = max(n, 2 * (0 if self._offsets is None else self._offsets.numel() - 1))
             self._store = torch.zeros(cap_s, dtype=torch.float32, device=self.device)
             self._offsets = torch.zeros(cap_n + 1, dtype=torch.int64, device=self.device)
-        a = 0
+        self._resample_into(waves, len_in, sample_rate, plan, self._store)
+        return plan
+
+    def _resample_into(self, waves, len_in, sample_rate, plan, store, what='waves'):
+        """Upload in chunks of whole recordings and resample each chunk in one launch into store[:plan.offsets[-1]] (also
+        the RecordingScorer's path for the clean recordings: both sides of a score go through the same resampler)."""
+        a, n = 0, len(waves)
         while a < n:
             b, acc = a, 0
             while b < n and (b == a or acc + len_in[b] <= self.chunk_samples):
@@ -144,14 +168,13 @@ class Enhancer:
                 b += 1
             off_in = np.zeros(b - a + 1, dtype=np.int64)
             np.cumsum(len_in[a:b], out=off_in[1:])
-            parts = [_as_float32(waves[i], f'waves[{i}]') for i in range(a, b)]
+            parts = [_as_float32(waves[i], f'{what}[{i}]') for i in range(a, b)]
             for i, p in zip(range(a, b), parts):
                 if not np.isfinite(p).all():
-                    raise ValueError(f'waves[{i}]: found inf, neginf or nan in the audio')
+                    raise ValueError(f'{what}[{i}]: found inf, neginf or nan in the audio')
             x = torch.from_numpy(np.concatenate(parts)).to(self.device)
-            ops.resample_sinc(x, sample_rate, self.sr, offsets=off_in, out=self._store[int(plan.offsets[a]):int(plan.offsets[b])])
+            ops.resample_sinc(x, sample_rate, self.sr, offsets=off_in, out=store[int(plan.offsets[a]):int(plan.offsets[b])])
             a = b
-        return plan
 
     def _upload_tables(self, plan):
         """ONE pinned host-to-device copy of everything the kernels index with: [offsets (int64, the unused tail = total) |
@@ -271,17 +294,7 @@ class Enhancer:
         in_paths, out_paths = list(in_paths), list(out_paths)
         if len(in_paths) != len(out_paths) or not in_paths:
             raise ValueError(f'enhance_files: {len(in_paths)} inputs for {len(out_paths)} outputs')
-        waves, rate0 = [], None
-        for p in in_paths:
-            rate, data = wavfile.read(p)
-            if data.dtype != np.int16:
-                raise ValueError(f'{p}: {data.dtype} samples; only 16-bit PCM WAV is decoded')
-            if data.ndim != 1:
-                raise ValueError(f'{p}: {data.shape[1]} channels; only mono WAV is read')
-            if rate0 is not None and rate != rate0:
-                raise ValueError(f'{p}: {rate} Hz, the files before it {rate0} Hz; one sample rate per call')
-            rate0 = rate
-            waves.append(data)
+        waves, rate0 = read_pcm16(in_paths)
         plan, tables, _, speech = self.enhance_segments(waves, rate0)
         pcm = self.stitch(plan, tables, speech, pcm=True)[1].cpu().numpy()
         for p, a, b in zip(out_paths, plan.offsets[:-1], plan.offsets[1:]):

@@ -1,0 +1,99 @@
+"""How good is an enhanced recording: STOI and SI-SNR of whole recordings, scored where the Enhancer leaves them.
+
+    scorer = RecordingScorer(Enhancer(net, mode='dcs'))          (or a MagnitudeEnhancer)
+    scores = scorer.score(noisy_waves, clean_waves, sample_rate=48000)
+        -> {'stoi', 'stoi_noisy', 'sisnr', 'sisnr_noisy'}: float32 [n] device tensors; the _noisy entries score the
+           unprocessed input against clean, so scores['stoi'] - scores['stoi_noisy'] is what the network gained
+    scores, speech = scorer.score(noisy_waves, clean_waves, 48000, return_audio=True)
+    scores = scorer.score_files(noisy_paths, clean_paths)         mono 16-bit PCM WAV of one rate
+
+The Enhancer keeps everything ragged in one flat device buffer with an int64 offset table; the metrics speak the same
+convention (metrics.stoi_ragged / sisnr_ragged, csrc/stoi_ragged.hip), so a whole test set is scored in a handful of launches
+and nothing returns to the host before the caller asks for values.  Per call: enhancer.enhance_segments and stitch make the
+flat speech estimate; the clean recordings go through the same upload and the same ops.resample_sinc into a store of the
+scorer's own, at the plan's offsets; the estimate and the enhancer's resident (resampled) noisy signal are scored against it.
+PESQ, segmental SNR and the composite measures are not computed."""
+import numpy as np
+import torch
+
+from . import metrics
+from .audio_store import _signal_shape
+from .enhance import Enhancer, read_pcm16
+
+
+class RecordingScorer:
+    """enhancer: an Enhancer or a MagnitudeEnhancer, used as it is configured (mode, segment geometry, graph)."""
+
+    METRICS = ('stoi', 'stoi_noisy', 'sisnr', 'sisnr_noisy')
+
+    def __init__(self, enhancer):
+        if not isinstance(enhancer, Enhancer):
+            raise TypeError(f'RecordingScorer: expected an Enhancer or a MagnitudeEnhancer, got {type(enhancer).__name__}')
+        self.enhancer = enhancer
+        self._clean = None                                   # the clean recordings at config.sr, capacity kept across calls
+
+    @staticmethod
+    def _check_pairs(noisy_waves, clean_waves):
+        noisy_waves, clean_waves = list(noisy_waves), list(clean_waves)
+        if len(noisy_waves) != len(clean_waves):
+            raise ValueError(f'RecordingScorer: {len(noisy_waves)} noisy recordings for {len(clean_waves)} clean ones')
+        if not noisy_waves:
+            raise ValueError('RecordingScorer: no recordings')
+        len_in = np.zeros(len(noisy_waves), dtype=np.int64)
+        for i, (a, b) in enumerate(zip(noisy_waves, clean_waves)):
+            len_in[i] = _signal_shape(a, f'noisy_waves[{i}]')
+            if _signal_shape(b, f'clean_waves[{i}]') != len_in[i]:
+                raise ValueError(f'item {i}: clean_data and noisy_data are not the same length '
+                                 f'({b.shape[0]} and {a.shape[0]} samples)')
+        return noisy_waves, clean_waves, len_in
+
+    def score(self, noisy_waves, clean_waves, sample_rate, return_audio=False):
+        """Lists of 1-D float32 / int16 arrays or tensors at sample_rate, pairwise of equal length -> the dict of METRICS
+        (with return_audio: and the list of enhanced recordings, 1-D float32 device tensors at config.sr)."""
+        enh = self.enhancer
+        noisy_waves, clean_waves, len_in = self._check_pairs(noisy_waves, clean_waves)
+        plan, tables, _, segments = enh.enhance_segments(noisy_waves, sample_rate)
+        speech = enh.stitch(plan, tables, segments)
+        total, offsets = int(plan.offsets[-1]), tables[2]
+        if self._clean is None or self._clean.numel() < total:
+            self._clean = torch.zeros(max(total, 2 * (0 if self._clean is None else self._clean.numel())), dtype=torch.float32,
+                                      device=enh.device)
+        enh._resample_into(clean_waves, len_in, int(sample_rate), plan, self._clean, what='clean_waves')
+        clean, noisy = self._clean[:total], enh._store[:total]
+        longest = int(plan.lengths.max())
+        scores = {'stoi': metrics.stoi_ragged(clean, speech, offsets, enh.sr, longest=longest),
+                  'stoi_noisy': metrics.stoi_ragged(clean, noisy, offsets, enh.sr, longest=longest),
+                  'sisnr': metrics.sisnr_ragged(clean, speech, offsets),
+                  'sisnr_noisy': metrics.sisnr_ragged(clean, noisy, offsets)}
+        if return_audio:
+            return scores, enh._split(plan, speech)
+        return scores
+
+    def score_files(self, noisy_paths, clean_paths, return_audio=False):
+        """Mono 16-bit PCM WAV files of one sample rate (scipy.io.wavfile), noisy_paths[i] against clean_paths[i]."""
+        noisy_paths, clean_paths = list(noisy_paths), list(clean_paths)
+        if len(noisy_paths) != len(clean_paths) or not noisy_paths:
+            raise ValueError(f'score_files: {len(noisy_paths)} noisy files for {len(clean_paths)} clean ones')
+        noisy, rate = read_pcm16(noisy_paths)
+        clean, rate = read_pcm16(clean_paths, rate)
+        return self.score(noisy, clean, rate, return_audio=return_audio)
+
+
+def summarise(scores):
+    """Host summary of score()'s dict (the one device-to-host transfer): per metric the mean over the recordings that are not
+    NaN and the count of those that are (calc_metric's convention), and the two mean improvements over the pairs where both
+    sides are numbers.  -> (summary dict, per-recording float32 array [n, 4] in METRICS order)."""
+    keys = RecordingScorer.METRICS
+    table = torch.stack([scores[k].to(torch.float32) for k in keys], dim=1).cpu().numpy()
+
+    def mean(v):
+        ok = ~np.isnan(v)
+        return float(v[ok].astype(np.float64).sum()) / max(int(ok.sum()), 1)       # calc_metric's mean: NaNs left out
+
+    out = {'files': int(table.shape[0])}
+    for j, k in enumerate(keys):
+        out[k] = mean(table[:, j])
+        out[k + '_nan'] = int(np.isnan(table[:, j]).sum())
+    out['stoi_improvement'] = mean(table[:, 0] - table[:, 1])
+    out['sisnr_improvement'] = mean(table[:, 2] - table[:, 3])
+    return out, table

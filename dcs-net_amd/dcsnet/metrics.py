@@ -19,6 +19,11 @@ same framing, silent-frame test, window, band edges, clipping and segment statis
 test in fp64.  `stoi()` is its numerics contract (tests/test_stoi_device.py); parity with pystoi itself stays unpinned.
 `network_functions.calc_metric` uses it when `config.stoi_on_device` is set (default off: the host loop).
 
+Whole recordings.  `stoi_ragged()` / `sisnr_ragged()` score recordings of DIFFERENT lengths that lie in one flat device buffer
+with an int64 offset table (what dcsnet/enhance.py returns; csrc/stoi_ragged.hip): per recording bit-equal to `stoi_batch` of
+that recording alone, resp. the reference's SiSNR (network_functions.py:30-42) in fp64 without its batch mean.
+dcsnet/evaluate.py builds the scorer of enhanced recordings on them.
+
 PESQ.  ITU-T P.862 is ~2 k lines of reference C with psychoacoustic tables; it is not restated.  `pesq` stays the
 imported package when present, else None (calc_metric then reports NaN, as in round 1)."""
 import numpy as np
@@ -194,3 +199,53 @@ def stoi_batch(clean, estimate, fs_sig):
         h, up, down = resample_taps(fs_sig, clean.device)
         clean, estimate = ops.resample_poly(clean, h, up, down), ops.resample_poly(estimate, h, up, down)
     return ops.stoi(clean, estimate, bands)[0]
+
+
+# ---- whole recordings of different lengths ---------------------------------------------------------------------------
+
+def _ragged_args(what, clean, estimate, offsets, longest):
+    """-> (clean, estimate, offsets int64 [n + 1] on the device, longest).  offsets on the device are never read back: longest
+    (a host integer >= the longest recording) then defaults to the buffer's size, which is correct and slow (it sizes a
+    grid).  offsets on the host (a sequence, an array or a CPU tensor) are checked, uploaded, and give longest themselves."""
+    from ._lib import DcsHipError
+    import torch
+    if not (isinstance(clean, torch.Tensor) and isinstance(estimate, torch.Tensor) and clean.is_cuda and estimate.is_cuda):
+        raise DcsHipError(f'{what}: expected CUDA (HIP) tensors; the device path has no CPU fallback (use stoi())')
+    if clean.shape != estimate.shape or clean.dim() != 1:
+        raise ValueError(f'{what}: clean {tuple(clean.shape)} and estimate {tuple(estimate.shape)} must be flat buffers of '
+                         f'equal size')
+    clean = clean.to(torch.float32).contiguous()
+    estimate = estimate.to(torch.float32).contiguous()
+    if not (isinstance(offsets, torch.Tensor) and offsets.is_cuda):
+        off = np.asarray(offsets.numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64).reshape(-1)
+        if off.size < 2 or off[0] != 0 or off[-1] != clean.numel() or (np.diff(off) < 0).any():
+            raise ValueError(f'{what}: offsets must rise from 0 to the buffers\' size {clean.numel()}')
+        if longest is None:
+            longest = int(np.diff(off).max())
+        offsets = torch.from_numpy(off).to(clean.device)
+    return clean, estimate, offsets, clean.numel() if longest is None else int(longest)
+
+
+def stoi_ragged(clean, estimate, offsets, fs_sig, longest=None):
+    """stoi(clean[a:b], estimate[a:b], fs_sig) for every recording [a, b) = offsets[i:i + 2] of two flat device buffers: a
+    float32 [n] device tensor, recording by recording bit-equal to stoi_batch of that recording alone as [1, L], in a
+    handful of launches whatever n is (csrc/stoi_ragged.hip) and without a host read-back (capturable when offsets are on
+    the device).  offsets: int64 [n + 1], on the device or on the host; longest: see _ragged_args.  CPU signals raise
+    DcsHipError."""
+    from . import ops
+    clean, estimate, offsets, longest = _ragged_args('stoi_ragged', clean, estimate, offsets, longest)
+    bands = stoi_band_edges(clean.device)
+    if int(fs_sig) != FS:
+        h, up, down = resample_taps(fs_sig, clean.device)
+        clean, off10 = ops.resample_poly_ragged(clean, offsets, h, up, down)
+        estimate, _ = ops.resample_poly_ragged(estimate, offsets, h, up, down)
+        offsets, longest = off10, -(-longest * up // down)
+    return ops.stoi_ragged(clean, estimate, offsets, longest, bands)[0]
+
+
+def sisnr_ragged(clean, estimate, offsets):
+    """The reference's SiSNR (network_functions.py:30-42) of every recording of two flat device buffers, without the batch
+    mean: float32 [n] dB on the device (one launch, fp64 sums; capturable when offsets are on the device)."""
+    from . import ops
+    clean, estimate, offsets, _ = _ragged_args('sisnr_ragged', clean, estimate, offsets, None)
+    return ops.sisnr_ragged(clean, estimate, offsets)

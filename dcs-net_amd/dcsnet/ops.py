@@ -1377,6 +1377,83 @@ def stoi(clean10, est10, bands=None):
     return d, kept
 
 
+# ---- whole recordings of different lengths (csrc/stoi_ragged.hip, dcsnet/evaluate.py) ---------------------------------
+
+def _chk_ragged(what, offsets, *signals):
+    """Signals: 1-D float32 buffers of one size on one device; offsets: int64 [n + 1] there.  -> (n, total)."""
+    for i, x in enumerate(signals):
+        _chk(x, f'{what}: signal {i}', 1)
+        if x.shape != signals[0].shape or x.device != signals[0].device:
+            raise _lib.DcsHipError(f'{what}: signals of shapes {[tuple(s.shape) for s in signals]} on different devices or of '
+                                   f'different sizes')
+    if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda:
+        raise _lib.DcsHipError(f'{what}: offsets must be a CUDA (HIP) tensor (the kernels read them on the device)')
+    if (offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 2 or
+            offsets.device != signals[0].device):
+        raise _lib.DcsHipError(f'{what}: offsets must be a contiguous int64 [n + 1] tensor on {signals[0].device}')
+    n = offsets.numel() - 1
+    if n > 32767:
+        raise _lib.DcsHipError(f'{what}: {n} recordings in one call (at most 32767)')
+    return n, signals[0].numel()
+
+
+def resample_poly_ragged(x, offsets, h, up, down):
+    """resample_poly for recordings of different lengths in one flat buffer: x float [total], offsets int64 [n + 1] on the
+    device (recording i = x[offsets[i]:offsets[i + 1]]) -> (y float [ceil(total up / down) + n], y_offsets int64 [n + 1]):
+    recording i's ceil(L_i up / down) samples at y[y_offsets[i]:y_offsets[i + 1]], bit-equal to resample_poly of that recording
+    alone.  The offsets are never read on the host, so y is sized by its upper bound; its tail past y_offsets[n] is zero
+    (dcs_resample_poly_ragged_f32)."""
+    n, total = _chk_ragged('resample_poly_ragged', offsets, x)
+    _chk(h, 'h', 1)
+    up, down = int(up), int(down)
+    if up <= 0 or down <= 0:
+        raise _lib.DcsHipError(f'resample_poly_ragged: up={up}, down={down}')
+    cap = -(-total * up // down) + n
+    y = torch.zeros(cap, dtype=torch.float32, device=x.device)
+    y_off = torch.empty(n + 1, dtype=torch.int64, device=x.device)
+    check(_lib.load().dcs_resample_poly_ragged_f32(ptr(x) if total else None, ptr(offsets), n, total, ptr(y), ptr(y_off), cap,
+                                                   ptr(h), h.numel(), up, down, cur_stream()), 'dcs_resample_poly_ragged_f32')
+    return y, y_off
+
+
+def stoi_ragged(clean10, est10, offsets, longest, bands=None):
+    """STOI of n recordings of different lengths at 10 kHz: clean10 / est10 float [total], offsets int64 [n + 1] on the device,
+    longest: a host integer >= the longest recording (it sizes a grid) -> (d float [n], kept int32 [n]), recording by recording
+    bit-equal to stoi() of that recording alone as [1, L] (dcs_stoi_ragged_f32)."""
+    n, total = _chk_ragged('stoi_ragged', offsets, clean10, est10)
+    dev = clean10.device
+    if bands is None:
+        from .metrics import stoi_band_edges
+        bands = stoi_band_edges(dev)
+    if bands.dtype != torch.int32 or tuple(bands.shape) != (2, 15) or not bands.is_contiguous() or bands.device != dev:
+        raise _lib.DcsHipError(f'stoi_ragged: bands must be a contiguous int32 [2, 15] tensor on {dev}')
+    longest = int(longest)
+    if longest < 0:
+        raise _lib.DcsHipError(f'stoi_ragged: longest={longest}')
+    d = torch.empty(n, dtype=torch.float32, device=dev)
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.dcs_stoi_ragged_workspace_bytes(n, total)
+    if nbytes < 0:
+        raise _lib.DcsHipError(f'stoi_ragged: unsupported size ({n} recordings, {total} samples)')
+    ws = _workspace(nbytes, dev)
+    sig = (ptr(clean10), ptr(est10)) if total else (None, None)
+    check(lib.dcs_stoi_ragged_f32(*sig, ptr(offsets), n, total, min(longest, total), ptr(bands[0]), ptr(bands[1]), ptr(d),
+                                  ptr(kept), ptr(ws), ws.numel(), cur_stream()), 'dcs_stoi_ragged_f32')
+    return d, kept
+
+
+def sisnr_ragged(clean, est, offsets):
+    """The reference's SiSNR (network_functions.py:30-42, eps = 1e-8) of n recordings of different lengths, without its batch
+    mean: clean / est float [total], offsets int64 [n + 1] on the device -> float [n] dB; sums and logarithm in fp64
+    (dcs_sisnr_ragged_f32)."""
+    n, total = _chk_ragged('sisnr_ragged', offsets, clean, est)
+    out = torch.empty(n, dtype=torch.float32, device=clean.device)
+    sig = (ptr(clean), ptr(est)) if total else (None, None)
+    check(_lib.load().dcs_sisnr_ragged_f32(*sig, ptr(offsets), n, total, ptr(out), cur_stream()), 'dcs_sisnr_ragged_f32')
+    return out
+
+
 # ---- HBM-resident training audio (csrc/audio_store.hip, dcsnet/audio_store.py) ----------------------------------------
 
 _SINC_LOWPASS_WIDTH, _SINC_ROLLOFF = 6, 0.99                 # torchaudio 0.9.0's Resample defaults (config.py:61)

@@ -850,6 +850,38 @@ int dcs_stoi_f32(const float* clean10, const float* est10, int B, long L10, cons
                  float* out_d, int* out_kept, void* workspace, long workspace_bytes, dcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Scoring whole recordings of different lengths (dcsnet/evaluate.py), stoi_ragged.hip: the calls above for the ragged
+ * convention.  Signals are float[total] with int64 offsets[n + 1] on the device; recording i is [offsets[i], offsets[i + 1]),
+ * offsets non-decreasing inside [0, total], 1 <= n <= 32767, 0 <= total <= 2^40.  Grids are sized from the host integers of
+ * the argument lists; every per-recording size is read from the offsets on the device (offsets outside [0, total] are clamped
+ * into it; no value there makes a kernel leave its buffers).  No atomics, no sync, no read-back (capturable); fixed
+ * reduction orders (bit-reproducible).  A recording goes through the device code of the batched calls (csrc/stoi_common.h):
+ * its results are bit-equal to dcs_resample_poly_f32 with rows = 1 and dcs_stoi_f32 with B = 1 on its samples.
+ * dcs_resample_poly_ragged_f32: recording i of x -> ceil(L_i up / down) samples of y at out_offsets[i]; out_offsets long[n + 1]
+ *   (device) is WRITTEN by the call: the cumulated output lengths.  out_capacity: the floats y holds, at least
+ *   ceil(total up / down) + n (an upper bound of out_offsets[n]; the tail of y past out_offsets[n] is left as it was).  Taps never
+ *   reach across a recording's ends.  up, down <= 65536.  Two launches.
+ * dcs_stoi_ragged_workspace_bytes: pure host arithmetic, the workspace of dcs_stoi_ragged_f32 for (n, total10): it grows with
+ *   the total length (frame base long[n + 1] | energies double[Fc] | kept indices int[Fc] | band envelopes float[2][Fc][15],
+ *   Fc = total10 / 128), not with n x the longest recording; < 0 for bad arguments.
+ * dcs_stoi_ragged_f32: out_d float[n], out_kept int[n] = dcs_stoi_f32's outputs per recording at 10 kHz.  total10: the floats
+ *   clean10 / est10 hold (>= offsets[n]).  longest10 >= the longest recording (it sizes the band kernel's grid; a longer
+ *   recording is scored on its first longest10 samples).  Recordings of at most 256 samples keep 0 frames; fewer than 30 STFT
+ *   frames kept give exactly 1e-5.  Four launches.
+ * dcs_sisnr_ragged_f32: out float[n] = the reference's SiSNR (network_functions.py:30-42, eps = 1e-8) per recording without its
+ *   batch mean: dot = <est, clean>, norm = <clean, clean>, s_target = dot clean / (norm + eps), e_noise = est - s_target element
+ *   by element, 10 log10(|s_target|^2 / (|e_noise|^2 + eps) + eps); every sum and the logarithm in fp64, one workgroup per
+ *   recording.  One launch. */
+int dcs_resample_poly_ragged_f32(const float* x, const long* offsets, int n, long total, float* y, long* out_offsets,
+                                 long out_capacity, const float* h, int taps, int up, int down, dcs_stream_t stream);
+long dcs_stoi_ragged_workspace_bytes(int n, long total10);
+int dcs_stoi_ragged_f32(const float* clean10, const float* est10, const long* offsets, int n, long total10, long longest10,
+                        const int* band_lo, const int* band_hi, float* out_d, int* out_kept, void* workspace,
+                        long workspace_bytes, dcs_stream_t stream);
+int dcs_sisnr_ragged_f32(const float* clean, const float* est, const long* offsets, int n, long total, float* out,
+                         dcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * HBM-resident training audio (data.py:68-143: resample, crop, noise = noisy - clean, three torch.stft calls per item on the
  * loader workers; dcsnet/audio_store.py), audio_store.hip.
  * dcs_resample_sinc_f32: torchaudio.transforms.Resample(orig * g, new_ * g) of torchaudio 0.9.0 (sinc_interpolation, lowpass

@@ -1,0 +1,124 @@
+"""Scoring a set of recordings of different lengths (metrics.stoi_ragged, csrc/stoi_ragged.hip) against the two loops that were
+possible before it: per recording one metrics.stoi_batch([1, L]) call, and per recording a copy to the host and metrics.stoi
+there.  All three start from the same flat device buffers at 16 kHz (what the Enhancer leaves) and end with the per-recording
+scores on the device (the host loop: in a list).
+
+The set is synthetic and seeded: --recordings lengths spread uniformly over 1 to 10 s.  Timing: device events around one pass
+over the whole set; the three methods alternate in three rounds, in each of which a method repeats its pass until it has
+filled its third of --min-seconds (at least 1 s of every method, after a warm-up pass of each); medians over the passes.
+Launch counts are the kernels each method issues per pass (from the entry points' definitions, include/dcsnet_hip.h).
+
+usage: python tools/score_bench.py [--out profiles/score_bench.json] [--recordings 32]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'dcs-net_amd'))
+from dcsnet import metrics  # noqa: E402
+
+
+def synthetic_set(n, seed, rate=16000):
+    """Harmonic 'speech' under a syllable-rate envelope with a broadband part 30 dB down, and a noisy copy at -5 .. 20 dB."""
+    rng = np.random.default_rng(seed)
+    seconds = np.linspace(1.0, 10.0, n)[rng.permutation(n)]
+    clean, est = [], []
+    for i, s in enumerate(seconds):
+        L = int(round(s * rate))
+        t = np.arange(L) / rate
+        f0 = rng.uniform(100, 220)
+        x = sum(np.sin(2 * np.pi * k * f0 * t + rng.uniform(0, 6.3)) / k for k in range(1, 9))
+        x = (x + 0.03 * np.std(x) * rng.standard_normal(L)) * (0.6 + 0.4 * np.sin(2 * np.pi * rng.uniform(3, 6) * t))
+        noise = rng.standard_normal(L) * (np.linalg.norm(x) / np.sqrt(L)) * 10 ** (-np.linspace(-5, 20, n)[i] / 20)
+        clean.append((0.1 * x).astype(np.float32))
+        est.append((0.1 * (x + noise)).astype(np.float32))
+    return clean, est
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'score_bench.json'))
+    ap.add_argument('--recordings', type=int, default=32)
+    ap.add_argument('--min-seconds', type=float, default=1.0)
+    ap.add_argument('--seed', type=int, default=0)
+    a = ap.parse_args()
+    dev = torch.device('cuda:0')
+    fs = 16000
+    clean, est = synthetic_set(a.recordings, a.seed, fs)
+    off_h = np.zeros(a.recordings + 1, dtype=np.int64)
+    np.cumsum([len(c) for c in clean], out=off_h[1:])
+    c = torch.from_numpy(np.concatenate(clean)).to(dev)
+    e = torch.from_numpy(np.concatenate(est)).to(dev)
+    off = torch.from_numpy(off_h).to(dev)
+    longest = int(np.diff(off_h).max())
+    spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
+
+    def ragged():
+        return metrics.stoi_ragged(c, e, off, fs, longest=longest)
+
+    def per_recording():
+        return torch.cat([metrics.stoi_batch(c[p:q][None], e[p:q][None], fs) for p, q in spans])
+
+    def host_loop():
+        return [metrics.stoi(c[p:q].cpu().numpy(), e[p:q].cpu().numpy(), fs) for p, q in spans]
+
+    methods = (('ragged_call', ragged), ('per_recording_stoi_batch', per_recording), ('host_loop', host_loop))
+    first = {}
+    for name, fn in methods:
+        first[name] = fn()
+        torch.cuda.synchronize()
+        print(f'[score_bench] warm-up of {name} done', file=sys.stderr, flush=True)
+    # The methods differ by orders of magnitude per pass, so they alternate in ROUNDS: in each round every method repeats
+    # its pass (each pass timed by its own event pair) until it has filled its share of --min-seconds.
+    rounds = 3
+    times = {name: [] for name, _ in methods}
+    for r in range(rounds):
+        for name, fn in methods:
+            spent = 0.0
+            while spent < a.min_seconds / rounds:
+                s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                fn()
+                t.record()
+                t.synchronize()
+                times[name].append(s.elapsed_time(t) / 1e3)
+                spent += times[name][-1]
+        print(f'[score_bench] round {r + 1} of {rounds} done', file=sys.stderr, flush=True)
+    sisnr = []
+    for _ in range(20):
+        s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        metrics.sisnr_ragged(c, e, off)
+        t.record()
+        t.synchronize()
+        sisnr.append(s.elapsed_time(t) * 1e3)
+    n = a.recordings
+    res = {'metric': 'score_recordings', 'device': torch.cuda.get_device_name(0), 'recordings': n,
+           'audio_seconds': round(float(off_h[-1]) / fs, 2), 'lengths_s': '1 .. 10 s at 16 kHz, uniform, seeded',
+           'ragged_equals_per_recording': bool(torch.equal(first['ragged_call'], first['per_recording_stoi_batch'])),
+           'max_abs_diff_vs_host': float(np.max(np.abs(first['ragged_call'].cpu().numpy() - np.array(first['host_loop'])))),
+           'timing': 'device events around one pass over the set; methods alternate in 3 rounds, each filling a third of '
+                     'min_seconds with repeated passes; median over the passes', 'min_seconds': a.min_seconds,
+           'kernel_launches': {'ragged_call': 2 * 2 + 4, 'ragged_call_fills': 2, 'per_recording_stoi_batch': 5 * n,
+                               'host_loop_copies': 2 * n},
+           'sisnr_ragged_us_median': round(float(np.median(sisnr)), 2)}
+    for name, _ in methods:
+        med = float(np.median(times[name]))
+        res[name] = {'passes': len(times[name]), 'timed_s': round(sum(times[name]), 2), 'ms_per_pass_median': round(med * 1e3, 3),
+                     'ms_per_pass_min': round(min(times[name]) * 1e3, 3), 'recordings_per_s': round(n / med, 1)}
+    for name in ('per_recording_stoi_batch', 'host_loop'):
+        res[f'speedup_ragged_vs_{name}'] = round(res[name]['ms_per_pass_median'] / res['ragged_call']['ms_per_pass_median'], 2)
+    print(json.dumps(res))
+    if a.out != '-':
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()
