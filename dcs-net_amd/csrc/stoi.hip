@@ -14,6 +14,9 @@
 //                           zero-pad to 512, real FFT (fft512_common.h), |X|^2 summed over the 15 bands [lo, hi), sqrt
 //   stoi_score_kernel     one workgroup per utterance: the 30-frame segments (normalise, clip, remove the mean, correlate) in
 //                           fp64 and their mean; exactly 1e-5 when fewer than 30 STFT frames remain
+//   stoi_score_ext_kernel one workgroup per utterance, in place of stoi_score_kernel in dcs_stoi_ext_f32: that score and / or the
+//                           extended one (ESTOI: each segment normalised by rows, then by columns, in fp64; thread t takes the
+//                           segments t, t + 256, ...), whichever the caller asked for, from the same band envelopes
 //
 // Grids are sized from (B, L) alone; every kernel reads the device-side kept count and exits where there is no work.  No float
 // atomics, no cross-workgroup synchronisation: every reduction has a fixed order, results are bit-reproducible.
@@ -81,6 +84,37 @@ __global__ __launch_bounds__(256) void stoi_score_kernel(const float* __restrict
     score_frames(X, X + Mmax * kBands, kept[b], red, out_d + b);
 }
 
+// out_d / out_e: null = not asked for (not both)
+__global__ __launch_bounds__(256) void stoi_score_ext_kernel(const float* __restrict__ band_ws, const int* __restrict__ kept, long Mmax,
+                                                             float* __restrict__ out_d, float* __restrict__ out_e) {
+    __shared__ double red[256];
+    const long b = blockIdx.x;
+    const float* X = band_ws + (b * 2) * Mmax * kBands;
+    score_frames_both(X, X + Mmax * kBands, kept[b], red, out_d ? out_d + b : nullptr, out_e ? out_e + b : nullptr);
+}
+
+// the keep and band launches of both entry points, arguments checked by the caller: -> out_kept, the band envelopes in ws
+int launch_keep_bands(const float* clean10, const float* est10, int B, long L10, const int* band_lo, const int* band_hi,
+                      int* out_kept, const StoiLayout& s, char* ws, hipStream_t st) {
+    double* e_ws = reinterpret_cast<double*>(ws);
+    int* idx_ws = reinterpret_cast<int*>(ws + s.off_idx);
+    float* band_ws = reinterpret_cast<float*>(ws + s.off_band);
+    DCS_LAUNCH(stoi_keep_kernel, dim3(B), dim3(256), 0, st, clean10, L10, s.F, e_ws, idx_ws, out_kept);
+    DCS_CHECK_LAUNCH();
+    if (s.Mmax > 0) {
+        DCS_LAUNCH(stoi_bands_kernel, dim3((unsigned)((s.Mmax + kFramesPerWg - 1) / kFramesPerWg), 2 * B), dim3(256), 0, st, clean10,
+                   est10, L10, s.F, s.Mmax, idx_ws, out_kept, band_lo, band_hi, band_ws);
+        DCS_CHECK_LAUNCH();
+    }
+    return DCS_OK;
+}
+
+inline bool bad_stoi(const float* clean10, const float* est10, int B, long L10, const int* band_lo, const int* band_hi,
+                     const int* out_kept, const void* workspace) {
+    return B <= 0 || B > 32767 || L10 < 0 || L10 > (1L << 31) || !band_lo || !band_hi || !out_kept || !workspace ||
+           (L10 > 0 && (!clean10 || !est10));
+}
+
 }  // namespace
 
 extern "C" int dcs_resample_poly_f32(const float* x, float* y, int rows, long L, const float* h, int taps, int up, int down,
@@ -104,24 +138,30 @@ extern "C" long dcs_stoi_workspace_bytes(int B, long L10) {
 
 extern "C" int dcs_stoi_f32(const float* clean10, const float* est10, int B, long L10, const int* band_lo, const int* band_hi,
                             float* out_d, int* out_kept, void* workspace, long workspace_bytes, dcs_stream_t stream) {
-    if (B <= 0 || B > 32767 || L10 < 0 || L10 > (1L << 31) || !band_lo || !band_hi || !out_d || !out_kept || !workspace)
-        return DCS_ERR_BADARG;
-    if (L10 > 0 && (!clean10 || !est10)) return DCS_ERR_BADARG;
+    if (bad_stoi(clean10, est10, B, L10, band_lo, band_hi, out_kept, workspace) || !out_d) return DCS_ERR_BADARG;
     const StoiLayout s = stoi_layout(B, L10);
     if (workspace_bytes < s.bytes) return DCS_ERR_WORKSPACE;
     char* ws = static_cast<char*>(workspace);
-    double* e_ws = reinterpret_cast<double*>(ws);
-    int* idx_ws = reinterpret_cast<int*>(ws + s.off_idx);
-    float* band_ws = reinterpret_cast<float*>(ws + s.off_band);
     hipStream_t st = dcs_stream(stream);
-    DCS_LAUNCH(stoi_keep_kernel, dim3(B), dim3(256), 0, st, clean10, L10, s.F, e_ws, idx_ws, out_kept);
+    const int rc = launch_keep_bands(clean10, est10, B, L10, band_lo, band_hi, out_kept, s, ws, st);
+    if (rc != DCS_OK) return rc;
+    DCS_LAUNCH(stoi_score_kernel, dim3(B), dim3(256), 0, st, reinterpret_cast<const float*>(ws + s.off_band), out_kept, s.Mmax, out_d);
     DCS_CHECK_LAUNCH();
-    if (s.Mmax > 0) {
-        DCS_LAUNCH(stoi_bands_kernel, dim3((unsigned)((s.Mmax + kFramesPerWg - 1) / kFramesPerWg), 2 * B), dim3(256), 0, st, clean10,
-                   est10, L10, s.F, s.Mmax, idx_ws, out_kept, band_lo, band_hi, band_ws);
-        DCS_CHECK_LAUNCH();
-    }
-    DCS_LAUNCH(stoi_score_kernel, dim3(B), dim3(256), 0, st, band_ws, out_kept, s.Mmax, out_d);
+    return DCS_OK;
+}
+
+extern "C" int dcs_stoi_ext_f32(const float* clean10, const float* est10, int B, long L10, const int* band_lo, const int* band_hi,
+                                float* out_d, float* out_e, int* out_kept, void* workspace, long workspace_bytes,
+                                dcs_stream_t stream) {
+    if (bad_stoi(clean10, est10, B, L10, band_lo, band_hi, out_kept, workspace) || (!out_d && !out_e)) return DCS_ERR_BADARG;
+    const StoiLayout s = stoi_layout(B, L10);
+    if (workspace_bytes < s.bytes) return DCS_ERR_WORKSPACE;
+    char* ws = static_cast<char*>(workspace);
+    hipStream_t st = dcs_stream(stream);
+    const int rc = launch_keep_bands(clean10, est10, B, L10, band_lo, band_hi, out_kept, s, ws, st);
+    if (rc != DCS_OK) return rc;
+    DCS_LAUNCH(stoi_score_ext_kernel, dim3(B), dim3(256), 0, st, reinterpret_cast<const float*>(ws + s.off_band), out_kept, s.Mmax,
+               out_d, out_e);
     DCS_CHECK_LAUNCH();
     return DCS_OK;
 }

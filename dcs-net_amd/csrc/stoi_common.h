@@ -1,6 +1,6 @@
 // stoi_common.h — the device code that stoi.hip (B utterances of one length) and stoi_ragged.hip (recordings of any lengths in
-// one flat buffer) share: the constants, the resampler's output sample, and the three per-recording stages of STOI, each written
-// against ONE recording's pointers.  A kernel of either file only works out where its recording's samples, frame slots and band
+// one flat buffer) share: the constants, the resampler's output sample, and the three per-recording stages of STOI (with the
+// score stage's extended sibling, ESTOI), each written against ONE recording's pointers.  A kernel of either file only works out where its recording's samples, frame slots and band
 // rows lie and then calls the stage, so a recording goes through the same operations in the same order whichever entry point
 // scores it: dcs_stoi_ragged_f32 is bit-equal to dcs_stoi_f32 with B = 1 on the same samples.
 #pragma once
@@ -204,6 +204,100 @@ __device__ __forceinline__ void score_frames(const float* __restrict__ X, const 
         __syncthreads();
     }
     if (t == 0) *out_d = (float)(red[0] / (double)pairs);
+}
+
+// The row statistics of one signal of one segment of the extended score: frames 0 .. 29 of xs float[30][15] -> per band its mean
+// over the 30 frames and 1 / (norm of the centred row + eps).  Direct sums in ascending frame order, all in registers (the band
+// loops unroll).  A constant row has norm 0: its centred values are zeros and stay zeros, no NaN.
+__device__ __forceinline__ void segment_rows(const float* __restrict__ xs, double (&mean)[kBands], double (&rinv)[kBands]) {
+    double s[kBands];
+#pragma unroll
+    for (int j = 0; j < kBands; ++j) s[j] = 0.0;
+    for (int i = 0; i < kSeg; ++i) {
+#pragma unroll
+        for (int j = 0; j < kBands; ++j) s[j] += (double)xs[i * kBands + j];
+    }
+#pragma unroll
+    for (int j = 0; j < kBands; ++j) {
+        mean[j] = s[j] / kSeg;
+        s[j] = 0.0;
+    }
+    for (int i = 0; i < kSeg; ++i) {
+#pragma unroll
+        for (int j = 0; j < kBands; ++j) {
+            const double c = (double)xs[i * kBands + j] - mean[j];
+            s[j] = fma(c, c, s[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kBands; ++j) rinv[j] = 1.0 / (sqrt(s[j]) + kEps);
+}
+
+// one segment of the extended intermediate intelligibility (ESTOI, Jensen & Taal 2016): frames s .. s + 29 of all 15 bands.
+// Rows first (each band over its 30 frames: remove the mean, divide by norm + eps), then columns of the result (each frame
+// over the 15 bands: the same), then sum(x_n y_n) / 30.  A column's sum(x_n y_n) is formed as sum(x_c y_c) / ((|x_c| + eps)
+// (|y_c| + eps)) from its centred values: one division per column.
+__device__ __forceinline__ double segment_ext(const float* __restrict__ X, const float* __restrict__ Y, long s) {
+    const float* xs = X + s * kBands;
+    const float* ys = Y + s * kBands;
+    double mx[kBands], rx[kBands], my[kBands], ry[kBands];
+    segment_rows(xs, mx, rx);
+    segment_rows(ys, my, ry);
+    double acc = 0.0;
+    for (int i = 0; i < kSeg; ++i) {
+        double a[kBands], b[kBands], sa = 0.0, sb = 0.0;
+#pragma unroll
+        for (int j = 0; j < kBands; ++j) {
+            a[j] = ((double)xs[i * kBands + j] - mx[j]) * rx[j];
+            b[j] = ((double)ys[i * kBands + j] - my[j]) * ry[j];
+            sa += a[j];
+            sb += b[j];
+        }
+        const double ma = sa / kBands, mb = sb / kBands;
+        double saa = 0.0, sbb = 0.0, sab = 0.0;
+#pragma unroll
+        for (int j = 0; j < kBands; ++j) {
+            const double ac = a[j] - ma, bc = b[j] - mb;
+            saa = fma(ac, ac, saa);
+            sbb = fma(bc, bc, sbb);
+            sab = fma(ac, bc, sab);
+        }
+        acc += sab / ((sqrt(saa) + kEps) * (sqrt(sbb) + kEps));
+    }
+    return acc / kSeg;
+}
+
+// The extended score stage of one recording (metrics.stoi(..., extended=True)), by one workgroup of 256 threads: score_frames'
+// inputs -> *out_e; exactly 1e-5 when fewer than 30 STFT frames remain.  Thread t takes the segments t, t + 256, ... in
+// ascending order, each from its own direct sums (no sums sliding from one segment to the next: their rounding would depend
+// on the history), then the fixed LDS tree of score_frames.  A NaN in a segment makes the score NaN.  red: LDS, free to write.
+__device__ __forceinline__ void score_frames_ext(const float* __restrict__ X, const float* __restrict__ Y, int K, double* red,
+                                                 float* __restrict__ out_e) {
+    const int t = threadIdx.x;
+    const long Mb = K > 0 ? K - 1 : 0;
+    if (Mb < kSeg) {
+        if (t == 0) *out_e = 1e-5f;
+        return;
+    }
+    const long nseg = Mb - kSeg + 1;
+    double acc = 0.0;
+    for (long s = t; s < nseg; s += 256) acc += segment_ext(X, Y, s);
+    red[t] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) red[t] += red[t + w];
+        __syncthreads();
+    }
+    if (t == 0) *out_e = (float)(red[0] / (double)nseg);
+}
+
+// Either or both scores of one recording from one pass over its band envelopes (out_d / out_e: null = not asked for).  *out_d
+// is score_frames' value, bit for bit.
+__device__ __forceinline__ void score_frames_both(const float* __restrict__ X, const float* __restrict__ Y, int K, double* red,
+                                                  float* __restrict__ out_d, float* __restrict__ out_e) {
+    if (out_d) score_frames(X, Y, K, red, out_d);
+    __syncthreads();                                         // red[0] has been read before the next tree overwrites it
+    if (out_e) score_frames_ext(X, Y, K, red, out_e);
 }
 
 }  // namespace dcs_stoi

@@ -14,6 +14,8 @@
 //   stoi_bands_ragged_kernel      grid (frames of the LONGEST recording / 4, 2 n): stoi_bands_kernel; workgroups past a recording's
 //                                   kept frames exit
 //   stoi_score_ragged_kernel      one workgroup per recording: stoi_score_kernel
+//   stoi_score_ext_ragged_kernel  one workgroup per recording, in its place in dcs_stoi_ext_ragged_f32: stoi_score_ext_kernel (STOI
+//                                   and / or ESTOI, whichever is asked for, from the same band envelopes)
 //   sisnr_ragged_kernel           one workgroup per recording, two passes over its samples, every sum in fp64: thread t adds the
 //                                   elements t, t + 256, ... in ascending order, then a fixed LDS tree
 //
@@ -140,6 +142,16 @@ __global__ __launch_bounds__(256) void stoi_score_ragged_kernel(const float* __r
     score_frames(X, X + Fcap * kBands, kept[b], red, out_d + b);
 }
 
+// out_d / out_e: null = not asked for (not both)
+__global__ __launch_bounds__(256) void stoi_score_ext_ragged_kernel(const float* __restrict__ band_ws, const long* __restrict__ fbase,
+                                                                    long Fcap, const int* __restrict__ kept, float* __restrict__ out_d,
+                                                                    float* __restrict__ out_e) {
+    __shared__ double red[256];
+    const long b = blockIdx.x;
+    const float* X = band_ws + fbase[b] * kBands;
+    score_frames_both(X, X + Fcap * kBands, kept[b], red, out_d ? out_d + b : nullptr, out_e ? out_e + b : nullptr);
+}
+
 // every thread returns the sum of v over the workgroup; additions in a fixed order (red: LDS double[256])
 __device__ __forceinline__ double block_sum(double v, double* red) {
     const int t = threadIdx.x;
@@ -202,6 +214,34 @@ inline bool bad_ragged(const long* offsets, int n, long total) {
     return !offsets || n <= 0 || n > kMaxRecordings || total < 0 || total > kMaxTotal;
 }
 
+inline bool bad_stoi_ragged(const float* clean10, const float* est10, const long* offsets, int n, long total10, long longest10,
+                            const int* band_lo, const int* band_hi, const int* out_kept, const void* workspace) {
+    return bad_ragged(offsets, n, total10) || longest10 < 0 || longest10 > (1L << 31) || !band_lo || !band_hi || !out_kept ||
+           !workspace || (total10 > 0 && (!clean10 || !est10));
+}
+
+// the prefix, keep and band launches of both entry points, arguments checked by the caller: -> out_kept, the frame bases and
+// the band envelopes in ws
+int launch_prefix_keep_bands(const float* clean10, const float* est10, const long* offsets, int n, long total10, long longest10,
+                             const int* band_lo, const int* band_hi, int* out_kept, const RaggedLayout& s, char* ws, hipStream_t st) {
+    long* fbase = reinterpret_cast<long*>(ws);
+    double* e_ws = reinterpret_cast<double*>(ws + s.off_e);
+    int* idx_ws = reinterpret_cast<int*>(ws + s.off_idx);
+    float* band_ws = reinterpret_cast<float*>(ws + s.off_band);
+    DCS_LAUNCH(ragged_prefix_kernel<PrefixFrames>, dim3(1), dim3(256), 0, st, offsets, n, total10, PrefixFrames{longest10}, s.Fcap,
+               fbase);
+    DCS_CHECK_LAUNCH();
+    DCS_LAUNCH(stoi_keep_ragged_kernel, dim3(n), dim3(256), 0, st, clean10, offsets, total10, fbase, e_ws, idx_ws, out_kept);
+    DCS_CHECK_LAUNCH();
+    const long Mmax = stoi_frames(longest10 < total10 ? longest10 : total10) - 1;      // STFT frames of the longest recording
+    if (Mmax > 0) {
+        DCS_LAUNCH(stoi_bands_ragged_kernel, dim3((unsigned)((Mmax + kFramesPerWg - 1) / kFramesPerWg), 2 * n), dim3(256), 0, st, clean10,
+                   est10, offsets, total10, fbase, s.Fcap, idx_ws, out_kept, band_lo, band_hi, band_ws);
+        DCS_CHECK_LAUNCH();
+    }
+    return DCS_OK;
+}
+
 }  // namespace
 
 extern "C" int dcs_resample_poly_ragged_f32(const float* x, const long* offsets, int n, long total, float* y, long* out_offsets,
@@ -229,29 +269,33 @@ extern "C" long dcs_stoi_ragged_workspace_bytes(int n, long total10) {
 extern "C" int dcs_stoi_ragged_f32(const float* clean10, const float* est10, const long* offsets, int n, long total10,
                                    long longest10, const int* band_lo, const int* band_hi, float* out_d, int* out_kept,
                                    void* workspace, long workspace_bytes, dcs_stream_t stream) {
-    if (bad_ragged(offsets, n, total10) || longest10 < 0 || longest10 > (1L << 31) || !band_lo || !band_hi || !out_d || !out_kept ||
-        !workspace || (total10 > 0 && (!clean10 || !est10)))
+    if (bad_stoi_ragged(clean10, est10, offsets, n, total10, longest10, band_lo, band_hi, out_kept, workspace) || !out_d)
         return DCS_ERR_BADARG;
     const RaggedLayout s = ragged_layout(n, total10);
     if (workspace_bytes < s.bytes) return DCS_ERR_WORKSPACE;
     char* ws = static_cast<char*>(workspace);
-    long* fbase = reinterpret_cast<long*>(ws);
-    double* e_ws = reinterpret_cast<double*>(ws + s.off_e);
-    int* idx_ws = reinterpret_cast<int*>(ws + s.off_idx);
-    float* band_ws = reinterpret_cast<float*>(ws + s.off_band);
     hipStream_t st = dcs_stream(stream);
-    DCS_LAUNCH(ragged_prefix_kernel<PrefixFrames>, dim3(1), dim3(256), 0, st, offsets, n, total10, PrefixFrames{longest10}, s.Fcap,
-               fbase);
+    const int rc = launch_prefix_keep_bands(clean10, est10, offsets, n, total10, longest10, band_lo, band_hi, out_kept, s, ws, st);
+    if (rc != DCS_OK) return rc;
+    DCS_LAUNCH(stoi_score_ragged_kernel, dim3(n), dim3(256), 0, st, reinterpret_cast<const float*>(ws + s.off_band),
+               reinterpret_cast<const long*>(ws), s.Fcap, out_kept, out_d);
     DCS_CHECK_LAUNCH();
-    DCS_LAUNCH(stoi_keep_ragged_kernel, dim3(n), dim3(256), 0, st, clean10, offsets, total10, fbase, e_ws, idx_ws, out_kept);
-    DCS_CHECK_LAUNCH();
-    const long Mmax = stoi_frames(longest10 < total10 ? longest10 : total10) - 1;      // STFT frames of the longest recording
-    if (Mmax > 0) {
-        DCS_LAUNCH(stoi_bands_ragged_kernel, dim3((unsigned)((Mmax + kFramesPerWg - 1) / kFramesPerWg), 2 * n), dim3(256), 0, st, clean10,
-                   est10, offsets, total10, fbase, s.Fcap, idx_ws, out_kept, band_lo, band_hi, band_ws);
-        DCS_CHECK_LAUNCH();
-    }
-    DCS_LAUNCH(stoi_score_ragged_kernel, dim3(n), dim3(256), 0, st, band_ws, fbase, s.Fcap, out_kept, out_d);
+    return DCS_OK;
+}
+
+extern "C" int dcs_stoi_ext_ragged_f32(const float* clean10, const float* est10, const long* offsets, int n, long total10,
+                                       long longest10, const int* band_lo, const int* band_hi, float* out_d, float* out_e,
+                                       int* out_kept, void* workspace, long workspace_bytes, dcs_stream_t stream) {
+    if (bad_stoi_ragged(clean10, est10, offsets, n, total10, longest10, band_lo, band_hi, out_kept, workspace) || (!out_d && !out_e))
+        return DCS_ERR_BADARG;
+    const RaggedLayout s = ragged_layout(n, total10);
+    if (workspace_bytes < s.bytes) return DCS_ERR_WORKSPACE;
+    char* ws = static_cast<char*>(workspace);
+    hipStream_t st = dcs_stream(stream);
+    const int rc = launch_prefix_keep_bands(clean10, est10, offsets, n, total10, longest10, band_lo, band_hi, out_kept, s, ws, st);
+    if (rc != DCS_OK) return rc;
+    DCS_LAUNCH(stoi_score_ext_ragged_kernel, dim3(n), dim3(256), 0, st, reinterpret_cast<const float*>(ws + s.off_band),
+               reinterpret_cast<const long*>(ws), s.Fcap, out_kept, out_d, out_e);
     DCS_CHECK_LAUNCH();
     return DCS_OK;
 }

@@ -155,9 +155,11 @@ SIGNATURES = {
     'dcs_resample_poly_f32': (_I, [_P, _P, _I, _L, _P, _I, _I, _I, _P]),
     'dcs_stoi_workspace_bytes': (_L, [_I, _L]),
     'dcs_stoi_f32': (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _P, _L, _P]),
+    'dcs_stoi_ext_f32': (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
     'dcs_resample_poly_ragged_f32': (_I, [_P, _P, _I, _L, _P, _P, _L, _P, _I, _I, _I, _P]),
     'dcs_stoi_ragged_workspace_bytes': (_L, [_I, _L]),
     'dcs_stoi_ragged_f32': (_I, [_P, _P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _L, _P]),
+    'dcs_stoi_ext_ragged_f32': (_I, [_P, _P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
     'dcs_sisnr_ragged_f32': (_I, [_P, _P, _P, _I, _L, _P, _P]),
     'dcs_resample_sinc_f32':(_I, [_P, _P, _P, _P, _I, _L, _P, _I, _I, _I, _P]),
     'dcs_audio_stft_batch_f32': (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P]),

@@ -6,13 +6,16 @@
            unprocessed input against clean, so scores['stoi'] - scores['stoi_noisy'] is what the network gained
     scores, speech = scorer.score(noisy_waves, clean_waves, 48000, return_audio=True)
     scores = scorer.score_files(noisy_paths, clean_paths)         mono 16-bit PCM WAV of one rate
+    scorer = RecordingScorer(enhancer, extended=True)             the dict gains 'estoi', 'estoi_noisy': the extended STOI
+        (ESTOI, metrics.stoi(..., extended=True)), from the same two STOI calls: each makes both scores in one pass
 
 The Enhancer keeps everything ragged in one flat device buffer with an int64 offset table; the metrics speak the same
 convention (metrics.stoi_ragged / sisnr_ragged, csrc/stoi_ragged.hip), so a whole test set is scored in a handful of launches
 and nothing returns to the host before the caller asks for values.  Per call: enhancer.enhance_segments and stitch make the
 flat speech estimate; the clean recordings go through the same upload and the same ops.resample_sinc into a store of the
 scorer's own, at the plan's offsets; the estimate and the enhancer's resident (resampled) noisy signal are scored against it.
-PESQ, segmental SNR and the composite measures are not computed."""
+summarise() takes its columns from the dict it is given.  PESQ, segmental SNR and the composite measures are not computed
+(DESIGN.md §7)."""
 import numpy as np
 import torch
 
@@ -22,14 +25,18 @@ from .enhance import Enhancer, read_pcm16
 
 
 class RecordingScorer:
-    """enhancer: an Enhancer or a MagnitudeEnhancer, used as it is configured (mode, segment geometry, graph)."""
+    """enhancer: an Enhancer or a MagnitudeEnhancer, used as it is configured (mode, segment geometry, graph).  extended: score
+    ESTOI as well; self.metrics names the dict's keys, METRICS or METRICS + EXTENDED."""
 
     METRICS = ('stoi', 'stoi_noisy', 'sisnr', 'sisnr_noisy')
+    EXTENDED = ('estoi', 'estoi_noisy')
 
-    def __init__(self, enhancer):
+    def __init__(self, enhancer, extended=False):
         if not isinstance(enhancer, Enhancer):
             raise TypeError(f'RecordingScorer: expected an Enhancer or a MagnitudeEnhancer, got {type(enhancer).__name__}')
         self.enhancer = enhancer
+        self.extended = bool(extended)
+        self.metrics = self.METRICS + self.EXTENDED if self.extended else self.METRICS
         self._clean = None                                   # the clean recordings at config.sr, capacity kept across calls
 
     @staticmethod
@@ -48,7 +55,7 @@ class RecordingScorer:
         return noisy_waves, clean_waves, len_in
 
     def score(self, noisy_waves, clean_waves, sample_rate, return_audio=False):
-        """Lists of 1-D float32 / int16 arrays or tensors at sample_rate, pairwise of equal length -> the dict of METRICS
+        """Lists of 1-D float32 / int16 arrays or tensors at sample_rate, pairwise of equal length -> the dict of self.metrics
         (with return_audio: and the list of enhanced recordings, 1-D float32 device tensors at config.sr)."""
         enh = self.enhancer
         noisy_waves, clean_waves, len_in = self._check_pairs(noisy_waves, clean_waves)
@@ -61,10 +68,17 @@ class RecordingScorer:
         enh._resample_into(clean_waves, len_in, int(sample_rate), plan, self._clean, what='clean_waves')
         clean, noisy = self._clean[:total], enh._store[:total]
         longest = int(plan.lengths.max())
-        scores = {'stoi': metrics.stoi_ragged(clean, speech, offsets, enh.sr, longest=longest),
-                  'stoi_noisy': metrics.stoi_ragged(clean, noisy, offsets, enh.sr, longest=longest),
+        if self.extended:
+            stoi, estoi = metrics.stoi_ragged(clean, speech, offsets, enh.sr, longest=longest, extended='both')
+            stoi_noisy, estoi_noisy = metrics.stoi_ragged(clean, noisy, offsets, enh.sr, longest=longest, extended='both')
+        else:
+            stoi = metrics.stoi_ragged(clean, speech, offsets, enh.sr, longest=longest)
+            stoi_noisy = metrics.stoi_ragged(clean, noisy, offsets, enh.sr, longest=longest)
+        scores = {'stoi': stoi, 'stoi_noisy': stoi_noisy,
                   'sisnr': metrics.sisnr_ragged(clean, speech, offsets),
                   'sisnr_noisy': metrics.sisnr_ragged(clean, noisy, offsets)}
+        if self.extended:
+            scores['estoi'], scores['estoi_noisy'] = estoi, estoi_noisy
         if return_audio:
             return scores, enh._split(plan, speech)
         return scores
@@ -82,8 +96,12 @@ class RecordingScorer:
 def summarise(scores):
     """Host summary of score()'s dict (the one device-to-host transfer): per metric the mean over the recordings that are not
     NaN and the count of those that are (calc_metric's convention), and the two mean improvements over the pairs where both
-    sides are numbers.  -> (summary dict, per-recording float32 array [n, 4] in METRICS order)."""
+    sides are numbers.  -> (summary dict, per-recording float32 array [n, 4] in METRICS order).  With the extended keys in
+    the dict ('estoi', 'estoi_noisy'): their columns behind the four, [n, 6], and estoi_improvement in the summary."""
     keys = RecordingScorer.METRICS
+    extended = all(k in scores for k in RecordingScorer.EXTENDED)
+    if extended:
+        keys = keys + RecordingScorer.EXTENDED
     table = torch.stack([scores[k].to(torch.float32) for k in keys], dim=1).cpu().numpy()
 
     def mean(v):
@@ -96,4 +114,6 @@ def summarise(scores):
         out[k + '_nan'] = int(np.isnan(table[:, j]).sum())
     out['stoi_improvement'] = mean(table[:, 0] - table[:, 1])
     out['sisnr_improvement'] = mean(table[:, 2] - table[:, 3])
+    if extended:
+        out['estoi_improvement'] = mean(table[:, 4] - table[:, 5])
     return out, table

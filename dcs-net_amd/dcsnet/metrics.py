@@ -13,6 +13,12 @@ numpy, as in the reference (which calls `.cpu().numpy()` per utterance), and is 
 imported.  PARITY UNPINNED: there is no pystoi here to compare with and the reference holds no STOI vectors; the
 tests check the algorithm's defining properties only (tests/test_host_cpu.py).
 
+ESTOI.  `stoi(..., extended=True)` is the extended STOI of Jensen & Taal (2016), pystoi's `extended=True`: the same front
+end, then every 15 x 30 segment normalised by rows and by columns instead of clipped and correlated per band.  It leaves out
+pystoi's EPS-sized random dither (see stoi()); parity is unpinned for the same reason (tests/test_estoi_cpu.py: properties and
+an independent route).  On the device it is `extended=True` / `'both'` of `stoi_batch` and `stoi_ragged` (one more score stage,
+csrc/stoi_common.h::score_frames_ext; tests/test_estoi_device.py).
+
 STOI on the device.  `stoi_batch()` restates `stoi()` below for a whole batch of device tensors [B, L] (csrc/stoi.hip,
 through ops.resample_poly and ops.stoi): the same resampler (its closed polyphase form with the same normalised window), the
 same framing, silent-frame test, window, band edges, clipping and segment statistics, with the frame energies and the keep
@@ -111,11 +117,10 @@ def _stft(x, win, nfft, overlap):
     return np.array([np.fft.rfft(_hann(win) * x[i:i + win], n=nfft) for i in range(0, len(x) - win, hop)])
 
 
-def stoi(x, y, fs_sig, extended=False):
-    """Short-Time Objective Intelligibility of the processed signal y against the clean signal x (1-D, equal length).
-    Same call as pystoi.stoi; extended=True (ESTOI) is not restated."""
-    if extended:
-        raise NotImplementedError('extended STOI is not restated; the reference calls stoi(clean, estimate, sr)')
+def _band_segments(x, y, fs_sig):
+    """What both scores share: resampling to 10 kHz, silent-frame removal, STFT and one-third-octave band envelopes of the clean
+    signal x and the processed signal y -> the two stacks [segments, NUMBAND, N_SEG] of all 30-frame segments, or None when
+    fewer than N_SEG STFT frames remain."""
     x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
     if x.shape != y.shape or x.ndim != 1:
         raise ValueError(f'stoi: x {x.shape} and y {y.shape} must be 1-D signals of equal length')
@@ -124,13 +129,44 @@ def stoi(x, y, fs_sig, extended=False):
     x, y = remove_silent_frames(x, y, DYN_RANGE, N_FRAME, N_FRAME // 2)
     xs, ys = _stft(x, N_FRAME, NFFT, 2), _stft(y, N_FRAME, NFFT, 2)
     if xs.ndim != 2 or xs.shape[0] < N_SEG:
-        return 1e-5                                        # pystoi: "Not enough STFT frames to compute intermediate intelligibility"
+        return None                                        # pystoi: "Not enough STFT frames to compute intermediate intelligibility"
     obm, _ = thirdoct(FS, NFFT, NUMBAND, MINFREQ)
     xt = np.sqrt(obm @ (np.abs(xs.T) ** 2))                # [bands, frames]
     yt = np.sqrt(obm @ (np.abs(ys.T) ** 2))
     M = xt.shape[1]
     xseg = np.stack([xt[:, m - N_SEG:m] for m in range(N_SEG, M + 1)])      # [segments, bands, N_SEG]
     yseg = np.stack([yt[:, m - N_SEG:m] for m in range(N_SEG, M + 1)])
+    return xseg, yseg
+
+
+def _row_col_normalise(seg):
+    """[segments, bands, frames]: every row (a band over its 30 frames), then every column of the result (a frame over the 15
+    bands), to zero mean and unit norm, dividing by (norm + EPS): a constant row or column becomes zeros, not NaN."""
+    seg = seg - seg.mean(axis=2, keepdims=True)
+    seg = seg / (np.linalg.norm(seg, axis=2, keepdims=True) + EPS)
+    seg = seg - seg.mean(axis=1, keepdims=True)
+    return seg / (np.linalg.norm(seg, axis=1, keepdims=True) + EPS)
+
+
+def stoi(x, y, fs_sig, extended=False):
+    """Short-Time Objective Intelligibility of the processed signal y against the clean signal x (1-D, equal length).
+    Same call as pystoi.stoi.
+
+    extended=True: the extended STOI (ESTOI; J. Jensen, C. H. Taal, "An Algorithm for Predicting the Intelligibility of Speech
+    Masked by Modulated Noise Maskers", IEEE/ACM TASLP 24(11), 2016) in pystoi 0.3.3's processing order: the same resampling,
+    silent-frame removal, STFT, bands and segments, then every segment normalised by rows and by columns and
+    d = sum(x_n * y_n / 30) / segments; no clipping stage.  ONE deliberate difference from pystoi: it adds EPS * standard_normal
+    noise before each of the two normalisations to dodge 0 / 0 on constant rows; that is left out here, because a metric must
+    be deterministic and the noise moves a score by about 1e-15.  A constant row then normalises to zeros (the norms are
+    divided as norm + EPS), without a NaN.  PARITY UNPINNED, for the same reason as for STOI: there is no pystoi here to compare
+    with; tests/test_estoi_cpu.py checks the defining properties and an independent route through np.corrcoef."""
+    segs = _band_segments(x, y, fs_sig)
+    if segs is None:
+        return 1e-5
+    xseg, yseg = segs
+    if extended:
+        xn, yn = _row_col_normalise(xseg), _row_col_normalise(yseg)
+        return float(np.sum(xn * yn / N_SEG) / xseg.shape[0])
     norm = np.linalg.norm(xseg, axis=2, keepdims=True) / (np.linalg.norm(yseg, axis=2, keepdims=True) + EPS)
     yn = yseg * norm
     clip = 10 ** (-BETA / 20)
@@ -181,10 +217,16 @@ def resample_taps(fs_sig, device):
     return t
 
 
-def stoi_batch(clean, estimate, fs_sig):
+def _extended_result(out, extended):
+    """ops.stoi / ops.stoi_ragged's tuple without its kept counts: the score, or the pair (stoi, estoi) for 'both'."""
+    return out[0] if extended is False or extended is True else (out[0], out[1])
+
+
+def stoi_batch(clean, estimate, fs_sig, extended=False):
     """stoi(clean[i], estimate[i], fs_sig) for every row of two device tensors [B, L] of equal shape: a float32 [B] device
-    tensor, computed by the HIP kernels of csrc/stoi.hip without a host read-back (capturable).  CPU tensors raise
-    DcsHipError: there is no host fallback here (stoi() is the host function)."""
+    tensor, computed by the HIP kernels of csrc/stoi.hip without a host read-back (capturable).  extended=True: ESTOI,
+    stoi(..., extended=True), instead; extended='both': the pair (stoi, estoi) from one resampling and one pass of the keep
+    and band kernels.  CPU tensors raise DcsHipError: there is no host fallback here (stoi() is the host function)."""
     from . import ops
     from ._lib import DcsHipError
     import torch
@@ -198,7 +240,9 @@ def stoi_batch(clean, estimate, fs_sig):
     if int(fs_sig) != FS:
         h, up, down = resample_taps(fs_sig, clean.device)
         clean, estimate = ops.resample_poly(clean, h, up, down), ops.resample_poly(estimate, h, up, down)
-    return ops.stoi(clean, estimate, bands)[0]
+    if extended is False:
+        return ops.stoi(clean, estimate, bands)[0]
+    return _extended_result(ops.stoi(clean, estimate, bands, extended=extended), extended)
 
 
 # ---- whole recordings of different lengths ---------------------------------------------------------------------------
@@ -226,12 +270,12 @@ def _ragged_args(what, clean, estimate, offsets, longest):
     return clean, estimate, offsets, clean.numel() if longest is None else int(longest)
 
 
-def stoi_ragged(clean, estimate, offsets, fs_sig, longest=None):
+def stoi_ragged(clean, estimate, offsets, fs_sig, longest=None, extended=False):
     """stoi(clean[a:b], estimate[a:b], fs_sig) for every recording [a, b) = offsets[i:i + 2] of two flat device buffers: a
     float32 [n] device tensor, recording by recording bit-equal to stoi_batch of that recording alone as [1, L], in a
     handful of launches whatever n is (csrc/stoi_ragged.hip) and without a host read-back (capturable when offsets are on
-    the device).  offsets: int64 [n + 1], on the device or on the host; longest: see _ragged_args.  CPU signals raise
-    DcsHipError."""
+    the device).  offsets: int64 [n + 1], on the device or on the host; longest: see _ragged_args.  extended: as for
+    stoi_batch (True: ESTOI; 'both': the pair (stoi, estoi) from one resampling and one pass).  CPU signals raise DcsHipError."""
     from . import ops
     clean, estimate, offsets, longest = _ragged_args('stoi_ragged', clean, estimate, offsets, longest)
     bands = stoi_band_edges(clean.device)
@@ -240,7 +284,9 @@ def stoi_ragged(clean, estimate, offsets, fs_sig, longest=None):
         clean, off10 = ops.resample_poly_ragged(clean, offsets, h, up, down)
         estimate, _ = ops.resample_poly_ragged(estimate, offsets, h, up, down)
         offsets, longest = off10, -(-longest * up // down)
-    return ops.stoi_ragged(clean, estimate, offsets, longest, bands)[0]
+    if extended is False:
+        return ops.stoi_ragged(clean, estimate, offsets, longest, bands)[0]
+    return _extended_result(ops.stoi_ragged(clean, estimate, offsets, longest, bands, extended=extended), extended)
 
 
 def sisnr_ragged(clean, estimate, offsets):

@@ -1347,10 +1347,28 @@ def resample_poly(x, h, up, down):
     return y
 
 
-def stoi(clean10, est10, bands=None):
+def _chk_extended(what, extended):
+    if not (extended is False or extended is True or extended == 'both'):
+        raise _lib.DcsHipError(f"{what}: extended must be False, True or 'both', got {extended!r}")
+    return extended
+
+
+def _ext_outputs(n, dev, extended):
+    """(d, e) float [n] output tensors of the *_ext entry points; the one that extended does not ask for is None."""
+    return (torch.empty(n, dtype=torch.float32, device=dev) if extended == 'both' else None,
+            torch.empty(n, dtype=torch.float32, device=dev))
+
+
+def _ext_result(d, e, kept, extended):
+    return (d, e, kept) if extended == 'both' else (e, kept)
+
+
+def stoi(clean10, est10, bands=None, extended=False):
     """STOI of B utterances of equal length at 10 kHz: float [B, L10] each -> (d float [B], kept int32 [B] frames kept by the
     silent-frame removal) (dcs_stoi_f32).  bands: int32 [2, 15] one-third-octave bin ranges [lo, hi) on the same device
-    (default: metrics.stoi_band_edges)."""
+    (default: metrics.stoi_band_edges).  extended=True: the extended STOI instead, (e, kept); extended='both': (d, e, kept), d
+    bit-equal to the default's (dcs_stoi_ext_f32: one pass of the keep and band kernels, the same three launches)."""
+    _chk_extended('stoi', extended)
     _chk(clean10, 'clean10', 2)
     _chk(est10, 'est10', 2)
     if clean10.shape != est10.shape:
@@ -1362,19 +1380,26 @@ def stoi(clean10, est10, bands=None):
     if bands.dtype != torch.int32 or tuple(bands.shape) != (2, 15) or not bands.is_contiguous() or bands.device != dev:
         raise _lib.DcsHipError(f'stoi: bands must be a contiguous int32 [2, 15] tensor on {dev}')
     B, L = clean10.shape
-    d = torch.empty(B, dtype=torch.float32, device=dev)
     kept = torch.empty(B, dtype=torch.int32, device=dev)
+    if extended is False:
+        d = torch.empty(B, dtype=torch.float32, device=dev)
+    else:
+        d, e = _ext_outputs(B, dev, extended)
     if B == 0:
-        return d, kept
+        return (d, kept) if extended is False else _ext_result(d, e, kept, extended)
     lib = _lib.load()
     nbytes = lib.dcs_stoi_workspace_bytes(B, L)
     if nbytes < 0:
         raise _lib.DcsHipError(f'stoi: unsupported shape [{B}, {L}]')
     ws = _workspace(nbytes, dev)
     sig = (ptr(clean10), ptr(est10)) if L else (None, None)
-    check(lib.dcs_stoi_f32(*sig, B, L, ptr(bands[0]), ptr(bands[1]), ptr(d), ptr(kept), ptr(ws), ws.numel(), cur_stream()),
-          'dcs_stoi_f32')
-    return d, kept
+    if extended is False:
+        check(lib.dcs_stoi_f32(*sig, B, L, ptr(bands[0]), ptr(bands[1]), ptr(d), ptr(kept), ptr(ws), ws.numel(), cur_stream()),
+              'dcs_stoi_f32')
+        return d, kept
+    check(lib.dcs_stoi_ext_f32(*sig, B, L, ptr(bands[0]), ptr(bands[1]), None if d is None else ptr(d), ptr(e), ptr(kept), ptr(ws),
+                               ws.numel(), cur_stream()), 'dcs_stoi_ext_f32')
+    return _ext_result(d, e, kept, extended)
 
 
 # ---- whole recordings of different lengths (csrc/stoi_ragged.hip, dcsnet/evaluate.py) ---------------------------------
@@ -1416,10 +1441,12 @@ def resample_poly_ragged(x, offsets, h, up, down):
     return y, y_off
 
 
-def stoi_ragged(clean10, est10, offsets, longest, bands=None):
+def stoi_ragged(clean10, est10, offsets, longest, bands=None, extended=False):
     """STOI of n recordings of different lengths at 10 kHz: clean10 / est10 float [total], offsets int64 [n + 1] on the device,
     longest: a host integer >= the longest recording (it sizes a grid) -> (d float [n], kept int32 [n]), recording by recording
-    bit-equal to stoi() of that recording alone as [1, L] (dcs_stoi_ragged_f32)."""
+    bit-equal to stoi() of that recording alone as [1, L] (dcs_stoi_ragged_f32).  extended=True: (e, kept), the extended STOI
+    instead; extended='both': (d, e, kept) (dcs_stoi_ext_ragged_f32: the same four launches), as for stoi()."""
+    _chk_extended('stoi_ragged', extended)
     n, total = _chk_ragged('stoi_ragged', offsets, clean10, est10)
     dev = clean10.device
     if bands is None:
@@ -1430,17 +1457,25 @@ def stoi_ragged(clean10, est10, offsets, longest, bands=None):
     longest = int(longest)
     if longest < 0:
         raise _lib.DcsHipError(f'stoi_ragged: longest={longest}')
-    d = torch.empty(n, dtype=torch.float32, device=dev)
     kept = torch.empty(n, dtype=torch.int32, device=dev)
+    if extended is False:
+        d = torch.empty(n, dtype=torch.float32, device=dev)
+    else:
+        d, e = _ext_outputs(n, dev, extended)
     lib = _lib.load()
     nbytes = lib.dcs_stoi_ragged_workspace_bytes(n, total)
     if nbytes < 0:
         raise _lib.DcsHipError(f'stoi_ragged: unsupported size ({n} recordings, {total} samples)')
     ws = _workspace(nbytes, dev)
     sig = (ptr(clean10), ptr(est10)) if total else (None, None)
-    check(lib.dcs_stoi_ragged_f32(*sig, ptr(offsets), n, total, min(longest, total), ptr(bands[0]), ptr(bands[1]), ptr(d),
-                                  ptr(kept), ptr(ws), ws.numel(), cur_stream()), 'dcs_stoi_ragged_f32')
-    return d, kept
+    if extended is False:
+        check(lib.dcs_stoi_ragged_f32(*sig, ptr(offsets), n, total, min(longest, total), ptr(bands[0]), ptr(bands[1]), ptr(d),
+                                      ptr(kept), ptr(ws), ws.numel(), cur_stream()), 'dcs_stoi_ragged_f32')
+        return d, kept
+    check(lib.dcs_stoi_ext_ragged_f32(*sig, ptr(offsets), n, total, min(longest, total), ptr(bands[0]), ptr(bands[1]),
+                                      None if d is None else ptr(d), ptr(e), ptr(kept), ptr(ws), ws.numel(), cur_stream()),
+          'dcs_stoi_ext_ragged_f32')
+    return _ext_result(d, e, kept, extended)
 
 
 def sisnr_ragged(clean, est, offsets):

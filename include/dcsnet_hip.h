@@ -842,12 +842,19 @@ int dcs_pack_plan_destroy(void* plan);
  *   removal keeps, for B utterances of L10 >= 0 samples at 10 kHz (float[B][L10] each; may be null when L10 = 0).
  *   band_lo / band_hi int[15]: the one-third-octave bands as bin ranges [lo, hi) (metrics.thirdoct(10000, 512, 15, 150)).
  *   Frame energies and the keep test in fp64, spectra in fp32, segment statistics in fp64; exactly 1e-5 when fewer than 30
- *   STFT frames remain.  Three launches sized from (B, L10) alone, fixed reduction orders (bit-reproducible), no sync. */
+ *   STFT frames remain.  Three launches sized from (B, L10) alone, fixed reduction orders (bit-reproducible), no sync.
+ * dcs_stoi_ext_f32: dcs_stoi_f32 with two outputs, either of which may be null (not both): out_d float[b] as above, bit for
+ *   bit, and out_e float[b] = stoi(clean10[b], est10[b], 10000, extended=True), the extended STOI (ESTOI, Jensen & Taal 2016:
+ *   every 15 x 30 segment normalised by rows, then by columns, in fp64 from direct sums; exactly 1e-5 when fewer than 30 STFT
+ *   frames remain; NaN input gives NaN).  The same workspace (dcs_stoi_workspace_bytes) and the same three launches: the score
+ *   kernel computes whichever outputs are asked for from one pass of the keep and band stages. */
 int dcs_resample_poly_f32(const float* x, float* y, int rows, long L, const float* h, int taps, int up, int down,
                           dcs_stream_t stream);
 long dcs_stoi_workspace_bytes(int B, long L10);
 int dcs_stoi_f32(const float* clean10, const float* est10, int B, long L10, const int* band_lo, const int* band_hi,
                  float* out_d, int* out_kept, void* workspace, long workspace_bytes, dcs_stream_t stream);
+int dcs_stoi_ext_f32(const float* clean10, const float* est10, int B, long L10, const int* band_lo, const int* band_hi,
+                     float* out_d, float* out_e, int* out_kept, void* workspace, long workspace_bytes, dcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Scoring whole recordings of different lengths (dcsnet/evaluate.py), stoi_ragged.hip: the calls above for the ragged
@@ -868,6 +875,9 @@ int dcs_stoi_f32(const float* clean10, const float* est10, int B, long L10, cons
  *   clean10 / est10 hold (>= offsets[n]).  longest10 >= the longest recording (it sizes the band kernel's grid; a longer
  *   recording is scored on its first longest10 samples).  Recordings of at most 256 samples keep 0 frames; fewer than 30 STFT
  *   frames kept give exactly 1e-5.  Four launches.
+ * dcs_stoi_ext_ragged_f32: dcs_stoi_ragged_f32 with out_d and / or out_e float[n] (either may be null, not both) =
+ *   dcs_stoi_ext_f32's outputs per recording, bit-equal to that call with B = 1.  The same workspace
+ *   (dcs_stoi_ragged_workspace_bytes), the same four launches.
  * dcs_sisnr_ragged_f32: out float[n] = the reference's SiSNR (network_functions.py:30-42, eps = 1e-8) per recording without its
  *   batch mean: dot = <est, clean>, norm = <clean, clean>, s_target = dot clean / (norm + eps), e_noise = est - s_target element
  *   by element, 10 log10(|s_target|^2 / (|e_noise|^2 + eps) + eps); every sum and the logarithm in fp64, one workgroup per
@@ -878,6 +888,9 @@ long dcs_stoi_ragged_workspace_bytes(int n, long total10);
 int dcs_stoi_ragged_f32(const float* clean10, const float* est10, const long* offsets, int n, long total10, long longest10,
                         const int* band_lo, const int* band_hi, float* out_d, int* out_kept, void* workspace,
                         long workspace_bytes, dcs_stream_t stream);
+int dcs_stoi_ext_ragged_f32(const float* clean10, const float* est10, const long* offsets, int n, long total10, long longest10,
+                            const int* band_lo, const int* band_hi, float* out_d, float* out_e, int* out_kept, void* workspace,
+                            long workspace_bytes, dcs_stream_t stream);
 int dcs_sisnr_ragged_f32(const float* clean, const float* est, const long* offsets, int n, long total, float* out,
                          dcs_stream_t stream);
 

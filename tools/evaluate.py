@@ -6,7 +6,8 @@ enhanced and of the unprocessed recordings against the clean ones, on the device
 
 Files are paired by name: every *.wav of noisy_dir needs its namesake in clean_dir, mono 16-bit PCM, one sample rate, each pair
 of one length.  Prints one JSON line: the file count, the mean of each metric over the files where it is a number (and how
-many were not), and the mean improvements stoi - stoi_noisy and sisnr - sisnr_noisy.  --csv writes the per-file table."""
+many were not), and the mean improvements stoi - stoi_noisy and sisnr - sisnr_noisy.  --csv writes the per-file table.
+--extended adds the extended STOI (ESTOI: estoi, estoi_noisy, estoi_improvement) to the JSON line and the table."""
 import argparse
 import json
 import os
@@ -39,6 +40,7 @@ def main():
     ap.add_argument('--mode', default='dcs', choices=['dcs', 'dc', 'drs', 'dr'],
                     help='dcs / drs: subtract the noise estimate; dc / dr: apply the mask (drs, dr: the real network, R_NETWORK)')
     ap.add_argument('--csv', default=None, help='write the per-file table here')
+    ap.add_argument('--extended', action='store_true', help='score the extended STOI (ESTOI) as well')
     ap.add_argument('--segment-frames', type=int, default=2000)
     ap.add_argument('--overlap-frames', type=int, default=300)
     ap.add_argument('--batch-segments', type=int, default=16)
@@ -66,10 +68,11 @@ def main():
         net.set_activation_dtype('bf16')
     enh = Enh(net, mode=a.mode, segment_frames=a.segment_frames, overlap_frames=a.overlap_frames,
               batch_segments=a.batch_segments, use_graph=not a.no_graph)
-    summary, table = summarise(RecordingScorer(enh).score_files(noisy, clean))
+    scorer = RecordingScorer(enh, extended=a.extended)
+    summary, table = summarise(scorer.score_files(noisy, clean))
     if a.csv:
         with open(a.csv, 'w') as f:
-            f.write('file,' + ','.join(RecordingScorer.METRICS) + '\n')
+            f.write('file,' + ','.join(scorer.metrics) + '\n')
             for name, row in zip(names, table):
                 f.write(name + ',' + ','.join(repr(float(v)) for v in row) + '\n')
     print(json.dumps(dict(summary, mode=a.mode, checkpoint=os.path.basename(a.checkpoint))))

@@ -8,7 +8,11 @@ over the whole set; the three methods alternate in three rounds, in each of whic
 filled its third of --min-seconds (at least 1 s of every method, after a warm-up pass of each); medians over the passes.
 Launch counts are the kernels each method issues per pass (from the entry points' definitions, include/dcsnet_hip.h).
 
-usage: python tools/score_bench.py [--out profiles/score_bench.json] [--recordings 32]"""
+--extended times a fourth method beside them, alternating in the same rounds: the ragged call with extended='both' (STOI and
+ESTOI from one pass of the resampling, keep and band kernels), and records its cost relative to the STOI-only ragged call.
+--parent-json takes the JSON this tool printed on another commit in the same session and records that commit's ragged pass.
+
+usage: python tools/score_bench.py [--out profiles/score_bench.json] [--recordings 32] [--extended] [--parent-json FILE]"""
 import argparse
 import json
 import os
@@ -46,6 +50,8 @@ def main():
     ap.add_argument('--recordings', type=int, default=32)
     ap.add_argument('--min-seconds', type=float, default=1.0)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--extended', action='store_true', help="time stoi_ragged(extended='both') beside the STOI-only call")
+    ap.add_argument('--parent-json', default=None, help="this tool's JSON of the parent commit, same box, same session")
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     fs = 16000
@@ -67,7 +73,12 @@ def main():
     def host_loop():
         return [metrics.stoi(c[p:q].cpu().numpy(), e[p:q].cpu().numpy(), fs) for p, q in spans]
 
+    def ragged_both():
+        return metrics.stoi_ragged(c, e, off, fs, longest=longest, extended='both')
+
     methods = (('ragged_call', ragged), ('per_recording_stoi_batch', per_recording), ('host_loop', host_loop))
+    if a.extended:
+        methods = methods[:1] + (('ragged_both', ragged_both),) + methods[1:]
     first = {}
     for name, fn in methods:
         first[name] = fn()
@@ -113,6 +124,19 @@ def main():
                      'ms_per_pass_min': round(min(times[name]) * 1e3, 3), 'recordings_per_s': round(n / med, 1)}
     for name in ('per_recording_stoi_batch', 'host_loop'):
         res[f'speedup_ragged_vs_{name}'] = round(res[name]['ms_per_pass_median'] / res['ragged_call']['ms_per_pass_median'], 2)
+    if a.extended:
+        d, est_e = first['ragged_both']
+        host_e = np.array([metrics.stoi(c[p:q].cpu().numpy(), e[p:q].cpu().numpy(), fs, extended=True) for p, q in spans])
+        res['kernel_launches']['ragged_both'] = 2 * 2 + 4
+        res['both_d_equals_ragged_call'] = bool(torch.equal(d, first['ragged_call']))
+        res['estoi_max_abs_diff_vs_host'] = float(np.max(np.abs(est_e.cpu().numpy() - host_e)))
+        res['both_over_stoi_only'] = round(res['ragged_both']['ms_per_pass_median'] / res['ragged_call']['ms_per_pass_median'], 3)
+    if a.parent_json:
+        with open(a.parent_json) as f:
+            parent = json.load(f)
+        res['parent_commit_ragged_call'] = parent['ragged_call']
+        res['ragged_call_over_parent_commit'] = round(res['ragged_call']['ms_per_pass_median'] /
+                                                      parent['ragged_call']['ms_per_pass_median'], 3)
     print(json.dumps(res))
     if a.out != '-':
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
