@@ -84,9 +84,12 @@ __global__ __launch_bounds__(kThreads) void crm_kernel(const float2* __restrict_
 }
 
 // d unit_dir(v) / dv applied to a cotangent: (g - u (u.g)) / |v|   (0 at the singular point)
+// The singular point is |v|^2 below the smallest normal float (|v| < 2^-63), not |v| == 0 alone: there the reference's atan2
+// backward, (x g_y - y g_x) / (x^2 + y^2), has lost its denominator (0 where the squares underflow, which autograd masks), and a
+// |v| of 4e-24 left in v_i when v_r = z_r + eps cancels exactly turned a cotangent of 1 into 1e17 (tests/test_tail_fp64.py).
 __device__ __forceinline__ float2 unit_dir_bwd(float x, float y, float2 g) {
     const float h = hypotf(x, y);
-    if (h == 0.f) return make_float2(0.f, 0.f);
+    if (h < 0x1p-63f) return make_float2(0.f, 0.f);
     const float ih = rcp1(h);
     const float ux = x * ih, uy = y * ih;
     const float d = ux * g.x + uy * g.y;
