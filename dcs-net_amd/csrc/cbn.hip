@@ -10,6 +10,7 @@
 //   cbn_apply_kernel     y = act(A x + c) (+ dropout), float4 streaming, coefficients in VGPRs
 // HBM-bound: algorithmic bytes per pixel-channel = 8 (stats read) + 8 + 8 (apply read + write).
 #include "dcs_common.h"
+#include "conv_epilogue.h"
 #include "cbn_geom.h"
 
 namespace {
@@ -291,7 +292,12 @@ __device__ __forceinline__ float act_fn(float v) {
     return v;
 }
 
-// y = act(A x + c); thread keeps the coefficients of its fixed channel pair in registers.
+template <int ACT>
+__device__ __forceinline__ float4 act4(float4 v) {
+    return make_float4(act_fn<ACT>(v.x), act_fn<ACT>(v.y), act_fn<ACT>(v.z), act_fn<ACT>(v.w));
+}
+
+// y = act(A x + c) with the map of conv_epilogue.h (one definition: a conv with the map folded in agrees bit for bit); thread keeps the coefficients of its fixed channel pair in registers.
 template <int ACT, bool DROP>
 __global__ __launch_bounds__(kThreads) void cbn_apply_kernel(const act_t* __restrict__ x, act_t* __restrict__ y,
                                                               const float* __restrict__ coef, long P, int C, int G,
@@ -302,14 +308,12 @@ __global__ __launch_bounds__(kThreads) void cbn_apply_kernel(const act_t* __rest
     const ActIn4<act_t> x4 = act_in4(x);
     const ActOut4<act_t> y4 = act_out4(y);
     if (C == 1) {
-        const float a0 = coef[0], a1 = coef[1], a2 = coef[2], a3 = coef[3], c0 = coef[4], c1 = coef[5];
+        float q[12];                                        // the one channel's map for both pixels of a float4
+#pragma unroll
+        for (int e = 0; e < 12; ++e) q[e] = coef[e % 6];
         const long nvec = P / 2;
         for (long i = (long)blockIdx.x * kThreads + t; i < nvec; i += (long)gridDim.x * kThreads) {
-            float4 v = x4[i], o;
-            o.x = act_fn<ACT>(fmaf(a0, v.x, fmaf(a1, v.y, c0)));
-            o.y = act_fn<ACT>(fmaf(a2, v.x, fmaf(a3, v.y, c1)));
-            o.z = act_fn<ACT>(fmaf(a0, v.z, fmaf(a1, v.w, c0)));
-            o.w = act_fn<ACT>(fmaf(a2, v.z, fmaf(a3, v.w, c1)));
+            float4 o = act4<ACT>(conv::affine4<false>(x4[i], q));
             if (DROP) {
                 const uint64_t e = (uint64_t)i * 4;
                 o.x *= dcs_keep_scale(seed, e, drop_p, inv_keep);
@@ -321,8 +325,8 @@ __global__ __launch_bounds__(kThreads) void cbn_apply_kernel(const act_t* __rest
         }
         if ((P & 1) && blockIdx.x == 0 && t == 0) {
             const float xr = dcs_ld1(x + 2 * (P - 1)), xi = dcs_ld1(x + 2 * (P - 1) + 1);
-            float yr = act_fn<ACT>(fmaf(a0, xr, fmaf(a1, xi, c0)));
-            float yi = act_fn<ACT>(fmaf(a2, xr, fmaf(a3, xi, c1)));
+            const float2 yv = conv::affine2(xr, xi, q);
+            float yr = act_fn<ACT>(yv.x), yi = act_fn<ACT>(yv.y);
             if (DROP) {
                 yr *= dcs_keep_scale(seed, (uint64_t)2 * (P - 1), drop_p, inv_keep);
                 yi *= dcs_keep_scale(seed, (uint64_t)2 * (P - 1) + 1, drop_p, inv_keep);
@@ -333,15 +337,10 @@ __global__ __launch_bounds__(kThreads) void cbn_apply_kernel(const act_t* __rest
         return;
     }
     const int g = t % G, r0 = t / G;
-    const float* ca = coef + 12 * g;   // channels 2g and 2g+1, 6 floats each
-    const float a0 = ca[0], a1 = ca[1], a2 = ca[2], a3 = ca[3], c0 = ca[4], c1 = ca[5];
-    const float e0 = ca[6], e1 = ca[7], e2 = ca[8], e3 = ca[9], f0 = ca[10], f1 = ca[11];
+    float q[12];
+    conv::load_affine4(coef, 4 * g, q);   // channels 2g and 2g+1, 6 floats each
     for (long r = (long)blockIdx.x * rows_per_iter + r0; r < P; r += (long)gridDim.x * rows_per_iter) {
-        float4 v = x4[r * G + g], o;
-        o.x = act_fn<ACT>(fmaf(a0, v.x, fmaf(a1, v.y, c0)));
-        o.y = act_fn<ACT>(fmaf(a2, v.x, fmaf(a3, v.y, c1)));
-        o.z = act_fn<ACT>(fmaf(e0, v.z, fmaf(e1, v.w, f0)));
-        o.w = act_fn<ACT>(fmaf(e2, v.z, fmaf(e3, v.w, f1)));
+        float4 o = act4<ACT>(conv::affine4<false>(x4[r * G + g], q));
         if (DROP) {
             const uint64_t e = (uint64_t)(r * G + g) * 4;
             o.x *= dcs_keep_scale(seed, e, drop_p, inv_keep);
@@ -369,17 +368,11 @@ __global__ __launch_bounds__(kThreads) void cbn_apply_pool_kernel(const act_t* _
     const int b = blockIdx.y, bx = blockIdx.x, gx = gridDim.x;
     const ActIn4<act_t> x4 = act_in4(x) + (long)b * HW * G;
     const ActOut4<act_t> y4 = act_out4(y) + (long)b * HW * G;
-    const float* ca = coef + 12 * g;
-    const float a0 = ca[0], a1 = ca[1], a2 = ca[2], a3 = ca[3], c0 = ca[4], c1 = ca[5];
-    const float e0 = ca[6], e1 = ca[7], e2 = ca[8], e3 = ca[9], f0 = ca[10], f1 = ca[11];
+    float q[12];
+    conv::load_affine4(coef, 4 * g, q);
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     for (long r = (long)bx * rpi + r0; r < HW; r += (long)gx * rpi) {
-        const float4 v = x4[r * G + g];
-        float4 o;
-        o.x = act_fn<ACT>(fmaf(a0, v.x, fmaf(a1, v.y, c0)));
-        o.y = act_fn<ACT>(fmaf(a2, v.x, fmaf(a3, v.y, c1)));
-        o.z = act_fn<ACT>(fmaf(e0, v.z, fmaf(e1, v.w, f0)));
-        o.w = act_fn<ACT>(fmaf(e2, v.z, fmaf(e3, v.w, f1)));
+        const float4 o = act4<ACT>(conv::affine4<false>(x4[r * G + g], q));
         y4[r * G + g] = o;
         s0 += stored(o.x); s1 += stored(o.y); s2 += stored(o.z); s3 += stored(o.w);
     }

@@ -18,6 +18,7 @@
 //          (no atomics: bitwise reproducible) + a reduce that writes the reference's parameter
 //          layout (conv_r / conv_i or conv_tran_r / conv_tran_i, and the two biases).
 #include "conv_common.h"
+#include "conv_epilogue.h"
 #include "pack_jobs.h"
 #include "wgrad_reduce.h"
 
@@ -78,10 +79,9 @@ __device__ __forceinline__ void cconv_direct_body(const ConvArgs& a, int tile_id
         for (int i = 0; i < COB; ++i) {
             const float2 bv = a.bias ? a.bias[co0 + i] : make_float2(0.f, 0.f);
             float vr = accr[i] + bv.x, vi = acci[i] + bv.y;
-            if (a.coef) {                                  // folded eval-mode CBN (conv_common.h)
-                const float* q = a.coef + 6 * (co0 + i);
-                const float ur = vr, ui = vi;
-                vr = fmaf(q[0], ur, fmaf(q[1], ui, q[4])); vi = fmaf(q[2], ur, fmaf(q[3], ui, q[5]));
+            if (a.coef) {                                  // folded eval-mode CBN
+                const float2 u = conv::affine2(vr, vi, a.coef + 6 * (co0 + i));
+                vr = u.x; vi = u.y;
             }
             conv::stc(out + i, make_float2(dcs_act(vr, a.act), dcs_act(vi, a.act)));
         }

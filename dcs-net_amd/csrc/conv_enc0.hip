@@ -12,8 +12,9 @@
 // v_mfma_f32_16x16x4_f32: 16 pixels x 16 columns x 4 k per instruction, 26 per 16-pixel tile (taps padded to 52): 94 % of
 // the issued MACs are useful.  Two M-tiles run interleaved (independent accumulators, LDS latency).  A tile = 8 x 32 output pixels (16 M-tiles, four per wave) over a 21 x 69 input patch (11.6 KB); workgroups are
 // persistent and load the next tile's patch under the current tile's MFMAs.
-// Epilogue as everywhere: bias, optional folded eval-mode CBN (conv_common.h), activation; 64-byte rows per pixel.
+// Epilogue as everywhere: bias, optional folded eval-mode CBN (conv_epilogue.h), activation; 64-byte rows per pixel.
 #include "conv_common.h"
+#include "conv_epilogue.h"
 
 namespace {
 
@@ -70,41 +71,19 @@ __device__ __forceinline__ void patch_load(const conv::Args& a, const TileDiv& d
 
 // bias, folded eval-mode CBN, activation and store of one lane's 2 x 4 accumulators (M-tiles h = 0, 1; rows kg*4 + r)
 template <int ACT, bool CHECK, bool STAT>
-__device__ __forceinline__ void store_pair(const conv::Args& a, const f32x4v* acc, act_t* yp, int ox, float bv, float c_re,
-                                           float c_im, float c_add, int li, float* st) {
+__device__ __forceinline__ void store_pair(const conv::Args& a, const f32x4v* acc, act_t* yp, int ox, float bv,
+                                           const conv::ColAffine& ca, int li, float* st) {
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            if (STAT) {                                     // CBN statistics of the raw, UN-biased output
-                const float raw = (!CHECK || ox + h * 16 + r < a.Wout) ? acc[h][r] : 0.f;
-                st[0] += raw; st[1] = fmaf(raw, raw, st[1]); st[2] = fmaf(raw, dcs_dpp_term<0xB1, 0xf>(raw), st[2]);
-            }
+            // CBN statistics of the raw, UN-biased output
+            if (STAT) conv::col_stat_add(st, (!CHECK || ox + h * 16 + r < a.Wout) ? acc[h][r] : 0.f);
             float v = acc[h][r] + bv;
-            if (a.coef) {
-                const float pv = dcs_dpp_term<0xB1, 0xf>(v);
-                v = (li & 1) ? fmaf(c_re, pv, fmaf(c_im, v, c_add)) : fmaf(c_re, v, fmaf(c_im, pv, c_add));
-            }
+            v = conv::col_affine(a.coef, v, li, ca);
             v = ACT < 0 ? dcs_act(v, a.act) : dcs_act(v, ACT);
             if (!CHECK || ox + h * 16 + r < a.Wout) dcs_st1(yp + (h * 16 + r) * 16, v);
         }
-}
-
-// one row of partial CBN sums per (persistent) workgroup: over the 4 row groups of a column by shuffles, over the waves in LDS
-__device__ __forceinline__ void stat_rows_out(const conv::Args& a, float* st, float* red, int t, int lane, int wave, int li) {
-#pragma unroll
-    for (int e = 0; e < 3; ++e) { st[e] += __shfl_xor(st[e], 16, 64); st[e] += __shfl_xor(st[e], 32, 64); }
-    __syncthreads();                                        // every wave is done with the patches
-    if (lane < 16) { red[(wave * 16 + li) * 3] = st[0]; red[(wave * 16 + li) * 3 + 1] = st[1]; red[(wave * 16 + li) * 3 + 2] = st[2]; }
-    __syncthreads();
-    if (t < 40) {                                           // channel c: {S_r, S_i, S_rr, S_ii, S_ri}
-        const int c = t / 5, e = t % 5;
-        const int colx = 2 * c + (e == 1 || e == 3), which = e < 2 ? 0 : (e < 4 ? 1 : 2);
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) sum += red[(w * 16 + colx) * 3 + which];
-        a.stat[(long)t * a.stat_stride + blockIdx.x] = sum;
-    }
 }
 
 // Persistent workgroups: tile = blockIdx.x, += gridDim.x.  The NEXT tile's patch is loaded into registers while this
@@ -145,11 +124,7 @@ __global__ __launch_bounds__(256, 4) void cconv_enc0_kernel(conv::Args a, TileDi
     }
     const float* biasf = reinterpret_cast<const float*>(a.bias);
     const float bv = biasf ? biasf[li] : 0.f;
-    float c_re = 1.f, c_im = 0.f, c_add = 0.f;                            // folded eval-mode CBN (conv_mfma.hip)
-    if (a.coef) {
-        const float* q = a.coef + 6 * (li >> 1);
-        if (li & 1) { c_re = q[2]; c_im = q[3]; c_add = q[5]; } else { c_re = q[0]; c_im = q[1]; c_add = q[4]; }
-    }
+    const conv::ColAffine ca = conv::load_col_affine(a.coef, li);         // folded eval-mode CBN
     int buf = 0;
     float st[3] = {0.f, 0.f, 0.f};                          // this lane's column: sum, sum of squares, sum of re * im
     long long d_fill = 0, d_comp = 0, d_n = 0;
@@ -204,13 +179,14 @@ __global__ __launch_bounds__(256, 4) void cconv_enc0_kernel(conv::Args a, TileDi
             const int oy = oy0 + py;
             if (oy < a.Hout) {
                 act_t* yp = reinterpret_cast<act_t*>(a.y) + (((long)b * a.Hout + oy) * a.Wout + ox0 + kg * 4) * 16 + li;
-                if (ox0 + TC <= a.Wout) store_pair<ACT, false, STAT>(a, acc, yp, 0, bv, c_re, c_im, c_add, li, st);
-                else store_pair<ACT, true, STAT>(a, acc, yp, ox0 + kg * 4, bv, c_re, c_im, c_add, li, st);
+                if (ox0 + TC <= a.Wout) store_pair<ACT, false, STAT>(a, acc, yp, 0, bv, ca, li, st);
+                else store_pair<ACT, true, STAT>(a, acc, yp, ox0 + kg * 4, bv, ca, li, st);
             }
         }
         d_comp += EDIAG_NOW() - e1;
     }
-    if (STAT) stat_rows_out(a, st, reinterpret_cast<float*>(patch[0]), t, lane, wave, li);
+    // one row of partial CBN sums per (persistent) workgroup (its first barrier: every wave is done with the patches)
+    if (STAT) conv::col_stat_rows_out(st, reinterpret_cast<float*>(patch[0]), a.stat + blockIdx.x, a.stat_stride, t, lane, wave, li);
 #ifdef DCS_ENC0_DIAG
     if (dbg && t == 0 && blockIdx.x < 4096) {
         long long* q = dbg + blockIdx.x * 8;
@@ -293,11 +269,7 @@ __global__ __launch_bounds__(256, 4) void cconv_enc0b_kernel(conv::Args a, TileD
     }
     const float* biasf = reinterpret_cast<const float*>(a.bias);
     const float bv = biasf ? biasf[li] : 0.f;
-    float c_re = 1.f, c_im = 0.f, c_add = 0.f;                            // folded eval-mode CBN (conv_mfma.hip)
-    if (a.coef) {
-        const float* q = a.coef + 6 * (li >> 1);
-        if (li & 1) { c_re = q[2]; c_im = q[3]; c_add = q[5]; } else { c_re = q[0]; c_im = q[1]; c_add = q[4]; }
-    }
+    const conv::ColAffine ca = conv::load_col_affine(a.coef, li);         // folded eval-mode CBN
     int buf = 0;
     float st[3] = {0.f, 0.f, 0.f};
     long long d_fill = 0, d_comp = 0, d_n = 0;
@@ -371,13 +343,14 @@ __global__ __launch_bounds__(256, 4) void cconv_enc0b_kernel(conv::Args a, TileD
             const int oy = oy0 + py;
             if (oy < a.Hout) {
                 act_t* yp = reinterpret_cast<act_t*>(a.y) + (((long)b * a.Hout + oy) * a.Wout + ox0 + kg * 4) * 16 + li;
-                if (ox0 + TC <= a.Wout) store_pair<ACT, false, STAT>(a, acc, yp, 0, bv, c_re, c_im, c_add, li, st);
-                else store_pair<ACT, true, STAT>(a, acc, yp, ox0 + kg * 4, bv, c_re, c_im, c_add, li, st);
+                if (ox0 + TC <= a.Wout) store_pair<ACT, false, STAT>(a, acc, yp, 0, bv, ca, li, st);
+                else store_pair<ACT, true, STAT>(a, acc, yp, ox0 + kg * 4, bv, ca, li, st);
             }
         }
         d_comp += EDIAG_NOW() - e1;
     }
-    if (STAT) stat_rows_out(a, st, reinterpret_cast<float*>(&patch[0][0][0]), t, lane, wave, li);
+    // one row of partial CBN sums per (persistent) workgroup (its first barrier: every wave is done with the patches)
+    if (STAT) conv::col_stat_rows_out(st, reinterpret_cast<float*>(&patch[0][0][0]), a.stat + blockIdx.x, a.stat_stride, t, lane, wave, li);
 #ifdef DCS_ENC0_DIAG
     if (dbg && t == 0 && blockIdx.x < 4096) {
         long long* q = dbg + blockIdx.x * 8;

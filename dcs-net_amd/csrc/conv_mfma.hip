@@ -19,6 +19,7 @@
 // fp32-input MFMA is exact fp32 (bit-for-bit an fmaf chain), 157 TFLOP/s peak: the same numerics
 // as the direct kernel at ~6x its VALU rate.
 #include "conv_common.h"
+#include "conv_epilogue.h"
 #include "pack_jobs.h"
 #include "conv_mfma_args.h"
 #include "conv_ring.h"
@@ -688,12 +689,7 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
         for (int e = 0; e < 12; ++e) q[e] = 0.f;
         if (m.ksplit <= 1 && n0 < m.N) {
             if (biasf) bv = *reinterpret_cast<const float4*>(biasf + n0);
-            // folded eval-mode CBN: out = fma(c_re, re, fma(c_im, im, c_add)) per component, the association order of
-            // cbn_apply_kernel, so the folded and the two-kernel forms agree bit for bit
-            if (a.coef) {
-#pragma unroll
-                for (int e = 0; e < 12; ++e) q[e] = a.coef[6 * (n0 >> 1) + e];
-            }
+            if (a.coef) conv::load_affine4(a.coef, n0, q);             // folded eval-mode CBN
         }
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
@@ -719,94 +715,10 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
                 }
                 const int pi = (wm * WM + i) * 32 + row;
                 const int oy = oy0 + (pi >> m.twshift), ox = ox0 + (pi & (m.TW - 1));
-                if (STAT && n0 < m.N && oy < k.Hc && ox < k.Wc) {      // moments of the UN-biased value (pivot = bias)
-                    float* q_ = sst[STAT ? j : 0];
-                    q_[0] += v.x; q_[1] += v.y;
-                    q_[2] = fmaf(v.x, v.x, q_[2]); q_[3] = fmaf(v.y, v.y, q_[3]); q_[4] = fmaf(v.x, v.y, q_[4]);
-                    q_[5] += v.z; q_[6] += v.w;
-                    q_[7] = fmaf(v.z, v.z, q_[7]); q_[8] = fmaf(v.w, v.w, q_[8]); q_[9] = fmaf(v.z, v.w, q_[9]);
-                }
+                if (STAT && n0 < m.N && oy < k.Hc && ox < k.Wc) conv::stat10_add(sst[STAT ? j : 0], v);
                 if (m.ksplit <= 1) {
                     v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                    if (a.coef) {
-                        const float4 u = v;
-                        // Scalar FMAs, kept apart by empty asm statements: paired by the compiler into v_pk_fma_f32 with op_sel
-                        // (low half = q1 * u.y + q4 taking the HIGH half of the {u.x, u.y} pair) the low half sporadically
-                        // came out as q4 alone — 16 lanes (48..63) of one row at a time, ~300 of 4 M outputs, different ones
-                        // every run — in the instances built on the bf16 MFMA (PR = 2, 64x64 tile, CH = 16) with other
-                        // workgroups' MFMAs in flight on the CU; never seen beside the fp32 MFMA, gone with scalar FMAs.
-#if defined(DCS_EXP_EPI) && DCS_EXP_EPI >= 3
-                        // 3 = the failing instruction pair replicated by hand: v_pk_add_f32 (bias) directly followed by the
-                        // v_pk_fma_f32 whose LOW lane reads the HIGH half of the sum (op_sel:[0,1,0]); 4 = the same with two wait
-                        // states between them; 5 = the same pk_add followed by four scalar v_fma_f32 (control).  One asm block
-                        // per pair, so the spacing is exactly what is written (the hazard recognizer does not look inside).
-                        typedef float f2v __attribute__((ext_vector_type(2)));
-                        v = *reinterpret_cast<const float4*>(tsm + row * TP + 4 * c4);      // un-biased again
-#define DCS_EPI_PAIR(VX, VY, BX, BY, QA0, QA1, QB0, QB1, QC0, QC1)                                                        \
-                        {                                                                                               \
-                            f2v uv = {VX, VY}, bb = {BX, BY}, qa = {QA0, QA1}, qb = {QB0, QB1}, qc = {QC0, QC1}, rr;     \
-                            if (DCS_EXP_EPI == 3)                                                                       \
-                                asm volatile("v_pk_add_f32 %1, %2, %1\n\tv_pk_fma_f32 %0, %3, %1, %5 op_sel:[0,1,0]\n\ts_nop 0\n\t" \
-                                             "v_pk_fma_f32 %0, %4, %1, %0 op_sel_hi:[1,0,1]\n\ts_nop 0"                  \
-                                             : "=&v"(rr), "+v"(uv) : "v"(bb), "v"(qa), "v"(qb), "v"(qc));               \
-                            else if (DCS_EXP_EPI == 4)                                                                  \
-                                asm volatile("v_pk_add_f32 %1, %2, %1\n\ts_nop 1\n\tv_pk_fma_f32 %0, %3, %1, %5 op_sel:[0,1,0]\n\ts_nop 0\n\t" \
-                                             "v_pk_fma_f32 %0, %4, %1, %0 op_sel_hi:[1,0,1]\n\ts_nop 0"                  \
-                                             : "=&v"(rr), "+v"(uv) : "v"(bb), "v"(qa), "v"(qb), "v"(qc));               \
-                            else if (DCS_EXP_EPI == 6) {      /* no cross-half selection: operands broadcast by v_mov first */ \
-                                f2v ui, ur;                                                                             \
-                                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(uv) : "v"(bb));                           \
-                                ui[0] = uv[1]; ui[1] = uv[1]; ur[0] = uv[0]; ur[1] = uv[0];                             \
-                                asm volatile("v_pk_fma_f32 %0, %1, %2, %3\n\ts_nop 0\n\tv_pk_fma_f32 %0, %4, %5, %0\n\ts_nop 0" \
-                                             : "=&v"(rr) : "v"(qa), "v"(ui), "v"(qc), "v"(qb), "v"(ur));                 \
-                            } else if (DCS_EXP_EPI == 7) {    /* first pair scalar, second = op_sel_hi:[1,0,1] (HIGH lane reads the LOW half) */ \
-                                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(uv) : "v"(bb));                           \
-                                rr[0] = fmaf(qa[0], uv[1], qc[0]);                                                       \
-                                asm volatile("" : "+v"(rr[0]));                                                          \
-                                rr[1] = fmaf(qa[1], uv[1], qc[1]);                                                       \
-                                asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]\n\ts_nop 0" : "+v"(rr) : "v"(qb), "v"(uv)); \
-                            } else if (DCS_EXP_EPI == 8) {    /* only the cross-half form, fed by registers written long before */ \
-                                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(uv) : "v"(bb));                           \
-                                asm volatile("s_nop 7\n\ts_nop 7\n\tv_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0]\n\ts_nop 7" \
-                                             : "=&v"(rr) : "v"(qa), "v"(uv), "v"(qc));                                   \
-                                rr[0] = fmaf(qb[0], uv[0], rr[0]);                                                       \
-                                asm volatile("" : "+v"(rr[0]));                                                          \
-                                rr[1] = fmaf(qb[1], uv[0], rr[1]);                                                       \
-                                asm volatile("" : "+v"(rr[1]));                                                          \
-                            } else {                                                                                    \
-                                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(uv) : "v"(bb));                           \
-                                rr[0] = fmaf(qb[0], uv[0], fmaf(qa[0], uv[1], qc[0]));                                   \
-                                asm volatile("" : "+v"(rr[0]));                                                          \
-                                rr[1] = fmaf(qb[1], uv[0], fmaf(qa[1], uv[1], qc[1]));                                   \
-                                asm volatile("" : "+v"(rr[1]));                                                          \
-                            }                                                                                           \
-                            VX = rr[0]; VY = rr[1];                                                                     \
-                        }
-                        DCS_EPI_PAIR(v.x, v.y, bv.x, bv.y, q[1], q[3], q[0], q[2], q[4], q[5])
-                        DCS_EPI_PAIR(v.z, v.w, bv.z, bv.w, q[7], q[9], q[6], q[8], q[10], q[11])
-#undef DCS_EPI_PAIR
-#elif defined(DCS_EXP_EPI) && DCS_EXP_EPI >= 1
-                        // tools/pk_hazard_probe.py builds: 1 = the failing form (the compiler pairs the FMAs into v_pk_fma_f32
-                        // with op_sel directly behind the v_pk_add_f32 of the bias), 2 = the same pairing with wait states
-                        // between the bias add and the FMAs
-                        float4 w = u;
-#if DCS_EXP_EPI == 2
-                        asm volatile("s_nop 3" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w));
-#endif
-                        v.x = fmaf(q[0], w.x, fmaf(q[1], w.y, q[4]));
-                        v.y = fmaf(q[2], w.x, fmaf(q[3], w.y, q[5]));
-                        v.z = fmaf(q[6], w.z, fmaf(q[7], w.w, q[10]));
-                        v.w = fmaf(q[8], w.z, fmaf(q[9], w.w, q[11]));
-#else
-                        v.x = fmaf(q[0], u.x, fmaf(q[1], u.y, q[4]));
-                        asm volatile("" : "+v"(v.x));
-                        v.y = fmaf(q[2], u.x, fmaf(q[3], u.y, q[5]));
-                        asm volatile("" : "+v"(v.y));
-                        v.z = fmaf(q[6], u.z, fmaf(q[7], u.w, q[10]));
-                        asm volatile("" : "+v"(v.z));
-                        v.w = fmaf(q[8], u.z, fmaf(q[9], u.w, q[11]));
-#endif
-                    }
+                    if (a.coef) v = conv::affine4(v, q);
                     v.x = dcs_act(v.x, a.act); v.y = dcs_act(v.y, a.act); v.z = dcs_act(v.z, a.act); v.w = dcs_act(v.w, a.act);
                 }
                 if (n0 < m.N && oy < k.Hc && ox < k.Wc) {    // 32-bit offsets inside one image (launcher checks the extent)
@@ -825,21 +737,7 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
         float* const stat_row = a.stat + ((long)bz * gridDim.x + bx);
         const int stat_nt0 = (by % ny) * WAVES_N * WN;
 #pragma unroll
-        for (int j = 0; j < WN; ++j) {
-#pragma unroll
-            for (int e = 0; e < 10; ++e) tsm[e * 64 + lane] = sst[STAT ? j : 0][e];
-            float r0 = 0.f, r1 = 0.f;
-            const int k5 = lane >> 3;
-            if (lane < 40) {
-#pragma unroll
-                for (int q8 = 0; q8 < 8; ++q8) {
-                    r0 += tsm[k5 * 64 + c4 + 8 * q8];
-                    r1 += tsm[(5 + k5) * 64 + c4 + 8 * q8];
-                }
-                comb[(wave * WN + j) * 80 + lane] = r0;
-                comb[(wave * WN + j) * 80 + 40 + lane] = r1;
-            }
-        }
+        for (int j = 0; j < WN; ++j) conv::tile_stat_reduce(sst[STAT ? j : 0], tsm, comb, wave * WN + j, lane, c4);
         __syncthreads();
         for (int o = t; o < WAVES_N * WN * 80; o += 256) {
             const int ct = o / 80, e = o % 80, wn_ = ct / WN, j_ = ct % WN;
@@ -1144,11 +1042,7 @@ __global__ __launch_bounds__(256) void cconv_mfma16_kernel(MArgs m) {
     const int width = m.y2 == nullptr ? 16 : (second ? 16 - m.nsplit : m.nsplit);
     const int col = second ? n - m.nsplit : n;
     act_t* yb = yf + (long)b * a.Hout * a.Wout * width;
-    float c_re = 1.f, c_im = 0.f, c_add = 0.f;                        // folded eval-mode CBN (see the 32-column kernel)
-    if (a.coef) {
-        const float* q = a.coef + 6 * (n >> 1);
-        if (n & 1) { c_re = q[2]; c_im = q[3]; c_add = q[5]; } else { c_re = q[0]; c_im = q[1]; c_add = q[4]; }
-    }
+    const conv::ColAffine ca = conv::load_col_affine(a.coef, n);      // folded eval-mode CBN
     // (Measured and dropped, Round 5: the four classes' outputs assembled in an LDS image of the output tile and stored as 16-byte
     // pieces of whole 2-KB rows instead of 8 dword stores per lane and class that each touch four 64-byte half lines — same box:
     // dec5 forward 46.5 -> 49.9 us, enc1 data gradient 54.5 -> 57.5 us: the extra barrier pair, LDS round trip and address
@@ -1157,6 +1051,8 @@ __global__ __launch_bounds__(256) void cconv_mfma16_kernel(MArgs m) {
         constexpr int cc = decltype(ccv)::value;
         const conv::Cls& k = m.cls[c_first + cc];
         float* const stat_row = a.stat ? a.stat + ((long)(c_first + cc) * gridDim.x + blockIdx.x) : nullptr;   // (Cout = 8: 40 sums)
+        // The statistics stay written out here: conv::col_stat_add and conv::col_stat_rows_out (conv_epilogue.h, which this mirrors
+        // line for line) cost the CH = 32 instances 4 VGPRs each (120 -> 124 beside 8 AGPRs: a wave less per SIMD).
         float s1 = 0.f, s2 = 0.f, sri = 0.f;                           // CBN statistics of the raw output (a.stat)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -1169,10 +1065,7 @@ __global__ __launch_bounds__(256) void cconv_mfma16_kernel(MArgs m) {
                     s1 += raw; s2 = fmaf(raw, raw, s2); sri = fmaf(raw, dcs_dpp_term<0xB1, 0xf>(raw), sri);
                 }
                 float v = acc[cc][i][r] + bv;
-                if (a.coef) {
-                    const float pv = dcs_dpp_term<0xB1, 0xf>(v);
-                    v = (n & 1) ? fmaf(c_re, pv, fmaf(c_im, v, c_add)) : fmaf(c_re, v, fmaf(c_im, pv, c_add));
-                }
+                v = conv::col_affine(a.coef, v, n, ca);
 #if DCS_EXP_M16 & 1
                 if (oy < k.Hc && ox < k.Wc && v == 123456.f)          // (timing probe: no output stores)
 #else
@@ -1222,12 +1115,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     const long p = (i4 * 4) / N;
     const int n = (int)((i4 * 4) % N);
     if (bias) { v.x += bias[n]; v.y += bias[n + 1]; v.z += bias[n + 2]; v.w += bias[n + 3]; }
-    if (coef) {                                             // folded eval-mode CBN: two complex channels per thread
-        const float* q = coef + 6 * (n >> 1);
-        const float4 u = v;
-        v.x = fmaf(q[0], u.x, fmaf(q[1], u.y, q[4])); v.y = fmaf(q[2], u.x, fmaf(q[3], u.y, q[5]));
-        v.z = fmaf(q[6], u.z, fmaf(q[7], u.w, q[10])); v.w = fmaf(q[8], u.z, fmaf(q[9], u.w, q[11]));
-    }
+    if (coef) v = conv::affine4<false>(v, coef + 6 * (n >> 1));      // folded eval-mode CBN: two complex channels per thread
     v.x = dcs_act(v.x, act); v.y = dcs_act(v.y, act); v.z = dcs_act(v.z, act); v.w = dcs_act(v.w, act);
     if (y2 == nullptr) dcs_st4(y + i4 * 4, v);
     else if (n < nsplit) dcs_st4(y + p * nsplit + n, v);
@@ -1258,8 +1146,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* _
             const float4 u = *reinterpret_cast<const float4*>(part + (long)s_ * slab_floats + o);
             v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
         }
-        s[0] += v.x; s[1] += v.y; s[2] = fmaf(v.x, v.x, s[2]); s[3] = fmaf(v.y, v.y, s[3]); s[4] = fmaf(v.x, v.y, s[4]);
-        s[5] += v.z; s[6] += v.w; s[7] = fmaf(v.z, v.z, s[7]); s[8] = fmaf(v.w, v.w, s[8]); s[9] = fmaf(v.z, v.w, s[9]);
+        conv::stat10_add(s, v);
         v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
         dcs_st4(y + o, v);
     }
