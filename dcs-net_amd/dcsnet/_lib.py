@@ -29,6 +29,11 @@ class AttentionItem(ctypes.Structure):
                [(n, _I) for n in ('H', 'W', 'C', 'Ch')] + [('g_pooled', _P)]
 
 
+class SnapshotItem(ctypes.Structure):
+    """dcs_snapshot_item (include/dcsnet_hip.h): one tensor of a checkpoint snapshot launch."""
+    _fields_ = [('src', _P), ('words', _L), ('dst_word', _L), ('is_f32', _I), ('pad_', _I)]
+
+
 # name -> (restype, argtypes); must mirror include/dcsnet_hip.h exactly
 SIGNATURES = {
     'dcs_abi_version': (_I, []),
@@ -133,6 +138,7 @@ SIGNATURES = {
     'dcs_adam_amsgrad_step': (_I, [_P] * 6 + [_F, _F, _L, _P, _F, _F, _F, _F, _I, _P, _P, _P]),
     'dcs_adam_amsgrad_step_sumsq': (_I, [_P] * 6 + [_I, _F, _F, _L, _P, _F, _F, _F, _F, _I, _P, _P, _P]),
     'dcs_swa_average_f32': (_I, [_P, _P, _L, _L, _P]),
+    'dcs_snapshot_words': (_I, [_P, _I, _P, _P, _L, _P, _P]),
     'dcs_grad_sumsq_parts': (_I, [_P, _L, _P, _I, _P, _P, _P, _P, _I, _P]),
     'dcs_step_guard': (_I, [_P, _P, _P]),
     'dcs_stream_hold': (_I, [_P, _I, _P]),

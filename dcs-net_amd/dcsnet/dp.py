@@ -80,6 +80,9 @@ class FlatBucket:
         ordered = grouped + [p for _, p in named if id(p) not in taken]
         self.names = [name_of[id(p)] for p in ordered]
         self.params = ordered
+        # every parameter of the network in registration order: the index space of torch.optim.Adam(net.parameters())'s
+        # state_dict, which optimizer checkpoints are written in (adam_state_export / adam_state_import)
+        self.all_names = [n for n, _ in net.named_parameters()]
         # 4-float alignment of every slice keeps float4 access legal for any parameter shape
         offs, total = [], 0
         for p in self.params:
@@ -128,6 +131,80 @@ class FlatBucket:
                 events.append((e0, e1))
             return dist.get_world_size()
         return 1
+
+
+# ---- optimizer state in torch.optim.Adam's own state_dict format ---------------------------------------------------------
+# The reference trains with Adam(self.parameters(), amsgrad=True) (c_network.py:229-240) and Lightning stores that optimizer's
+# state_dict() under 'optimizer_states': param_groups[0]['params'] indexes ALL parameters in registration order, 'state' has
+# an entry {step, exp_avg, exp_avg_sq, max_exp_avg_sq} only for parameters that received a gradient — none for
+# decoder_attention.12/13.  Both optimizers below read and write exactly that, mapping by parameter NAME (the bucket's
+# order differs: LSTM groups first, slices padded to 4 floats), so the reference's checkpoints and this project's interchange.
+ADAM_STATE_FIELDS = ('exp_avg', 'exp_avg_sq', 'max_exp_avg_sq')
+
+
+def _adam_group(lr, betas, eps, weight_decay, n_params):
+    """param_groups[0] as this torch's Adam(amsgrad=True) writes it (the key set follows the installed torch)."""
+    g = dict(torch.optim.Adam([torch.zeros(1)], lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                              amsgrad=True).param_groups[0])
+    g['params'] = list(range(n_params))
+    return g
+
+
+def adam_state_export(bucket, group, step, field_of):
+    """torch.optim.Adam's state_dict over all of the network's parameters: field_of(name, field) -> the CPU tensor of a hot
+    parameter's moment (its own shape); step: the number of real updates — 0 means no state yet, as in torch."""
+    index = {n: i for i, n in enumerate(bucket.all_names)}
+    state = {}
+    if step > 0:
+        for name in bucket.names:
+            entry = {'step': torch.tensor(float(step), dtype=torch.float32)}
+            for f in ADAM_STATE_FIELDS:
+                entry[f] = field_of(name, f)
+            state[index[name]] = entry
+    return {'state': dict(sorted(state.items())), 'param_groups': [dict(group, params=list(range(len(bucket.all_names))))]}
+
+
+def adam_state_check(bucket, sd, betas, eps, weight_decay):
+    """Validate a torch.optim.Adam state_dict against the bucket and the instance's hyper-parameters; returns
+    (group, {hot name: entry}, step).  ValueError names the offending field."""
+    groups = sd.get('param_groups') if isinstance(sd, dict) else None
+    if not groups or len(groups) != 1 or 'state' not in sd:
+        raise ValueError("optimizer state: expected torch.optim.Adam's state_dict with one entry in 'param_groups'")
+    group = groups[0]
+    params = list(group.get('params', ()))
+    if len(params) != len(bucket.all_names):
+        raise ValueError(f"optimizer state: 'params' indexes {len(params)} parameters, the network has {len(bucket.all_names)}")
+    import struct
+
+    def f32(x):                 # the kernels receive fp32 values: 0.999 and its fp32 rounding are the same hyper-parameter
+        return struct.unpack('f', struct.pack('f', float(x)))[0]
+    mine = {'betas': tuple(betas), 'eps': eps, 'weight_decay': weight_decay}
+    for field, want in mine.items():
+        if field in group:
+            got = group[field]
+            same = (tuple(f32(b) for b in got) == tuple(f32(b) for b in want) if field == 'betas' else f32(got) == f32(want))
+            if not same:
+                raise ValueError(f'optimizer state: {field} = {got!r} differs from the optimizer\'s {want!r}')
+    if group.get('amsgrad') is False:
+        raise ValueError('optimizer state: amsgrad=False holds no max_exp_avg_sq; this optimizer is AMSGrad')
+    key_of = dict(zip(bucket.all_names, params))
+    shape_of = dict(zip(bucket.names, (p.shape for p in bucket.params)))
+    entries, steps = {}, set()
+    for name in bucket.names:
+        e = sd['state'].get(key_of[name])
+        if e is None:
+            continue                        # (never received a gradient: zero moments, as the fused kernel holds them)
+        for f in ('step',) + ADAM_STATE_FIELDS:
+            if f not in e:
+                raise ValueError(f'optimizer state: {name} has no {f}' + (' (amsgrad=False?)' if f == 'max_exp_avg_sq' else ''))
+        for f in ADAM_STATE_FIELDS:
+            if tuple(e[f].shape) != tuple(shape_of[name]):
+                raise ValueError(f'optimizer state: {name}.{f} has shape {tuple(e[f].shape)}, expected {tuple(shape_of[name])}')
+        steps.add(int(float(e['step'])))            # a 0-dim tensor, or the Python int of torch 1.10
+        entries[name] = e
+    if len(steps) > 1:
+        raise ValueError(f'optimizer state: step differs between parameters ({sorted(steps)}); one update count serves the bucket')
+    return group, entries, (steps.pop() if steps else 0)
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -179,6 +256,55 @@ class FusedAdam(torch.optim.Optimizer):
         set to None (torch.optim.Optimizer.zero_grad would detach them)."""
         self.b.zero_grad()
 
+    def state_dict(self):
+        """torch.optim.Adam's own format (adam_state_export): the moments live in the flat buffers m / v / vmax outside
+        Optimizer.state, so the inherited method would return nothing.  `step` is t_dev, the number of real updates; the
+        values are CPU copies of each parameter's slice.  Synchronises (reads the device)."""
+        return self.export_images(self.m.detach().cpu(), self.v.detach().cpu(), self.vmax.detach().cpu(), int(self.t_dev),
+                                  self.export_group())
+
+    def export_group(self):
+        """param_groups[0] of the exported state: host values only."""
+        group = _adam_group(self.lr, self.betas, self.eps, self.wd, len(self.b.all_names))
+        group.update({k: v for k, v in self.param_groups[0].items() if k in ('initial_lr', 'swa_lr')})     # the schedulers' keys
+        return group
+
+    def export_images(self, m, v, vmax, step, group):
+        """state_dict() from CPU images of the three flat buffers (checkpoint.CheckpointWriter: its snapshot); touches no
+        device memory."""
+        b = self.b
+        host = {'exp_avg': m, 'exp_avg_sq': v, 'max_exp_avg_sq': vmax}
+        where = {n: (o, p.numel(), p.shape) for n, o, p in zip(b.names, b.offsets, b.params)}
+
+        def field_of(name, f):
+            o, n, shape = where[name]
+            return host[f][o:o + n].clone().view(shape)
+        return adam_state_export(b, group, step, field_of)
+
+    def load_state_dict(self, state_dict):
+        """From torch.optim.Adam's format, IN PLACE into m / v / vmax / t_dev (a captured graph holds their addresses); the
+        padding between slices stays zero.  The rate comes from the loaded group: the next sync_lr() writes it to the device.
+        Refuses (ValueError naming the field) unequal `step`s, a state without max_exp_avg_sq, and betas / eps / weight_decay
+        other than the instance's — the kernels read those from the instance."""
+        if self.m.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedAdam.load_state_dict under stream capture: the copies would be replayed with every step')
+        b = self.b
+        group, entries, step = adam_state_check(b, state_dict, self.betas, self.eps, self.wd)
+        with torch.no_grad():
+            for f, buf in zip(ADAM_STATE_FIELDS, (self.m, self.v, self.vmax)):
+                host = torch.zeros(b.numel, dtype=buf.dtype)
+                for name, o, p in zip(b.names, b.offsets, b.params):
+                    if name in entries:
+                        host[o:o + p.numel()].copy_(entries[name][f].detach().reshape(-1))
+                buf.copy_(host)
+            self.t_dev.fill_(step)
+        self.t = step
+        if 'lr' in group:
+            self.param_groups[0]['lr'] = group['lr']
+        for k in ('initial_lr', 'swa_lr'):                 # what schedulers keep in the group
+            if k in group:
+                self.param_groups[0][k] = group[k]
+
     def step(self, world=1, seed_state=None, counters=None):
         """One update, unless the bucket's skip flag is set (a NaN loss on some rank: the reference's trainer skips
         the update, c_network.py:257-261) — decided on the device, so the same launches serve a replayed graph.
@@ -222,14 +348,45 @@ class TorchAdam:
     reference of FusedAdam; never on the product path."""
 
     def __init__(self, bucket, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=0.0):
-        self.b, self.max_norm = bucket, max_norm
+        self.b, self.max_norm, self.t = bucket, max_norm, 0
         self.opt = torch.optim.Adam(bucket.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                     amsgrad=True)
 
     def sync_lr(self):
         """torch.optim.Adam reads param_groups[0]['lr'] itself at every step."""
 
+    @property
+    def updates(self):
+        """Real updates so far (FusedAdam's t_dev): the inner optimizer's step count."""
+        steps = {int(float(s['step'])) for s in self.opt.state.values() if 'step' in s}
+        return max(steps) if steps else 0
+
+    def state_dict(self):
+        """As FusedAdam.state_dict: the inner optimizer's state re-indexed from the bucket's order to all of the network's
+        parameters in registration order, by name."""
+        b = self.b
+        index = {n: i for i, n in enumerate(b.all_names)}
+        state = {}
+        for name, p in zip(b.names, b.params):              # (torch holds no entry before a parameter's first gradient)
+            s = self.opt.state.get(p)
+            if s:
+                state[index[name]] = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in s.items()}
+        group = {k: v for k, v in self.opt.param_groups[0].items() if k != 'params'}
+        return {'state': dict(sorted(state.items())), 'param_groups': [dict(group, params=list(range(len(b.all_names))))]}
+
+    def load_state_dict(self, state_dict):
+        """As FusedAdam.load_state_dict, same refusals; the inner optimizer loads the entries re-indexed to the bucket's order."""
+        b, g0 = self.b, self.opt.param_groups[0]
+        group, entries, _ = adam_state_check(b, state_dict, g0['betas'], g0['eps'], g0['weight_decay'])
+        inner = {k: v for k, v in g0.items() if k != 'params'}
+        inner.update({k: v for k, v in group.items() if k in ('lr', 'initial_lr', 'swa_lr')})
+        inner['params'] = list(range(len(b.params)))
+        self.opt.load_state_dict({'state': {i: dict(entries[n]) for i, n in enumerate(b.names) if n in entries},
+                                  'param_groups': [inner]})
+        self.t = self.updates
+
     def step(self, world=1, seed_state=None, counters=None):
+        self.t += 1                                       # calls, as FusedAdam.t
         if seed_state is not None:
             seed_state += 1
         if counters is not None:
@@ -286,6 +443,43 @@ class TrainStep:
         """The torch.optim.Optimizer of the step: its param_groups[0]['lr'] is the learning rate every later step uses (graph
         replays included), so ReduceLROnPlateau / SWALR attach to it.  FusedAdam is one; TorchAdam wraps torch.optim.Adam."""
         return self.opt if isinstance(self.opt, torch.optim.Optimizer) else self.opt.opt
+
+    def state_dict(self):
+        """What a step needs beyond net.state_dict() (weights and buffers stay there) to continue where it stands: the optimizer
+        in torch.optim.Adam's format, and the counters — calls (opt.t), updates (t_dev: calls minus the steps a NaN loss
+        skipped), the dropout seed offset, the network's dropout call count and torch's initial seed (the three the dropout
+        masks are drawn from).  Synchronises."""
+        opt = self.opt
+        updates = int(opt.t_dev) if hasattr(opt, 't_dev') else opt.updates
+        return {'optimizer': opt.state_dict(),
+                'counters': {'calls': int(opt.t), 'updates': updates,
+                             'seed_state': 0 if self.seed_state is None else int(self.seed_state),
+                             'drop_calls': getattr(self.net, '_drop_calls', None),
+                             'torch_initial_seed': torch.initial_seed()}}
+
+    def load_state_dict(self, sd):
+        """In place, before or after the graph was captured (the graph holds the addresses, not the values); never under
+        capture.  Parameters and buffers are the caller's to restore (net.load_state_dict copies in place)."""
+        if self.bucket.flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('TrainStep.load_state_dict under stream capture')
+        from . import functional
+        self.opt.load_state_dict(sd['optimizer'])
+        c = sd.get('counters') or {}
+        if c.get('updates') is not None and hasattr(self.opt, 't_dev'):
+            self.opt.t_dev.fill_(int(c['updates']))
+        self.opt.t = int(c['calls']) if c.get('calls') is not None else int(c.get('updates') or self.opt.t)
+        if self.seed_state is not None:
+            self.seed_state.fill_(int(c.get('seed_state') or 0))
+        if c.get('drop_calls') is not None and hasattr(self.net, '_drop_calls'):
+            self.net._drop_calls = int(c['drop_calls'])
+        saved_seed = c.get('torch_initial_seed')
+        if saved_seed is not None and saved_seed != torch.initial_seed():
+            import warnings
+            warnings.warn(f'TrainStep.load_state_dict: torch.initial_seed() is {torch.initial_seed()}, the state was saved under '
+                          f'{saved_seed}; the dropout masks will not continue the saved stream')
+        # parameters, moments and running statistics changed behind torch's version counters
+        functional.bump_param_generation()
+        functional.note_state_update()
 
     def _counting(self, on):
         """While the step's forward runs, the network leaves the `+= 1` of its num_batches_tracked buffers to the optimizer

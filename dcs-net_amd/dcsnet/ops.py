@@ -1737,6 +1737,85 @@ def swa_average(avg, p, n_averaged):
     return avg
 
 
+# ---- checkpoint snapshot (csrc/snapshot.hip, dcsnet/checkpoint.py) ------------------------------------------------------
+
+SNAPSHOT_BLOCK_WORDS = 1024          # DCS_SNAPSHOT_BLOCK_WORDS (include/dcsnet_hip.h)
+_SNAPSHOT_FLOAT = (torch.float32, torch.complex64)                  # 4-byte IEEE words: counted when non-finite
+_SNAPSHOT_OTHER = (torch.int32, torch.int64, torch.float64, torch.complex128)      # copied, never counted
+
+
+class SnapshotTable:
+    """The device tables of one dcs_snapshot_words launch over `tensors` (kept alive here: the tables hold their addresses).
+    layout[i] = (first word, words) of tensor i in the staging slab, every start a multiple of 4 words; total_words the slab's
+    size; view(staging, i) is tensor i's image in a slab (device or host), with its dtype and shape."""
+
+    def __init__(self, tensors, items, first_block, layout, total_words, is_f32):
+        self.tensors, self.items, self.first_block = tensors, items, first_block
+        self.layout, self.total_words, self.is_f32 = layout, total_words, is_f32
+        self.n = len(tensors)
+
+    def view(self, staging, i):
+        o, w = self.layout[i]
+        t = self.tensors[i]
+        return staging.view(torch.int32).reshape(-1)[o:o + w].view(t.dtype).view(t.shape)
+
+
+def snapshot_table(tensors):
+    """Build the tables once: every tensor a contiguous CUDA tensor of 4-, 8- or 16-byte elements on one device whose address
+    stays put (the flat bucket, in-place buffers).  1..1024 tensors; an empty tensor is legal."""
+    import ctypes
+    tensors = list(tensors)
+    if not 1 <= len(tensors) <= 1024:
+        raise _lib.DcsHipError(f'snapshot_table: 1..1024 tensors, got {len(tensors)}')
+    dev = tensors[0].device
+    rows, first, layout, flags, total, blocks = [], [0], [], [], 0, 0
+    for i, t in enumerate(tensors):
+        if not t.is_cuda or t.device != dev:
+            raise _lib.DcsHipError(f'snapshot_table: tensor {i} on {t.device}; expected CUDA (HIP) tensors of one device (no CPU fallback)')
+        if t.dtype not in _SNAPSHOT_FLOAT + _SNAPSHOT_OTHER:
+            raise _lib.DcsHipError(f'snapshot_table: tensor {i} has dtype {t.dtype}; elements must be whole 4-byte words')
+        if not t.is_contiguous():
+            raise _lib.DcsHipError(f'snapshot_table: tensor {i} is not contiguous')
+        words = t.numel() * t.element_size() // 4
+        f32 = int(t.dtype in _SNAPSHOT_FLOAT)
+        rows.append((t.data_ptr() if words else _snapshot_null_item_ptr(tensors), words, total, f32))
+        layout.append((total, words))
+        flags.append(bool(f32))
+        blocks += (words + SNAPSHOT_BLOCK_WORDS - 1) // SNAPSHOT_BLOCK_WORDS
+        first.append(blocks)
+        total += (words + 3) // 4 * 4
+    buf = (_lib.SnapshotItem * len(rows))(*[_lib.SnapshotItem(p, w, o, f, 0) for p, w, o, f in rows])
+    raw = torch.frombuffer(bytearray(bytes(buf)), dtype=torch.uint8)
+    assert raw.numel() == 32 * len(rows), ctypes.sizeof(_lib.SnapshotItem)
+    return SnapshotTable(tensors, raw.to(dev), torch.tensor(first, dtype=torch.int64).to(dev), layout, total, flags)
+
+
+def _snapshot_null_item_ptr(tensors):
+    """A valid device address for an item of zero words (an empty tensor's data_ptr may be null): the first non-empty tensor's,
+    else any 4-byte aligned non-null value — nothing of a zero-word item is read."""
+    for t in tensors:
+        if t.numel():
+            return t.data_ptr()
+    return 16
+
+
+def snapshot(table, staging, counts):
+    """ONE launch on the current stream: every tensor of `table` into `staging` (>= table.total_words 4-byte words, 16-byte
+    aligned) at its layout offset, bit for bit, and counts int32[table.n] = non-finite words per float tensor (zeroed by the
+    call).  No synchronisation, no allocation: legal between two graph replays.  Words between tensors are left alone."""
+    for t, name in ((staging, 'staging'), (counts, 'counts')):
+        if not t.is_cuda or t.device != table.items.device or not t.is_contiguous():
+            raise _lib.DcsHipError(f'snapshot: {name} must be a contiguous CUDA (HIP) tensor on {table.items.device} (no CPU fallback)')
+    if counts.dtype != torch.int32 or counts.numel() < table.n:
+        raise _lib.DcsHipError(f'snapshot: counts must be int32 with >= {table.n} elements, got {counts.dtype} x {counts.numel()}')
+    words = staging.numel() * staging.element_size() // 4
+    if words < table.total_words or staging.data_ptr() % 16:
+        raise _lib.DcsHipError(f'snapshot: staging holds {words} words at {staging.data_ptr():#x}; needs {table.total_words}, 16-byte aligned')
+    check(_lib.load().dcs_snapshot_words(ptr(table.items), table.n, ptr(table.first_block), ptr(staging), words, ptr(counts),
+                                         cur_stream()), 'dcs_snapshot_words')
+    return staging
+
+
 # ---- complex <-> channels-last float views -------------------------------------------------
 
 def to_nhwc(z):

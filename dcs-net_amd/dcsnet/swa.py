@@ -114,9 +114,7 @@ class StochasticWeightAveraging:
                 swa_lrs = [swa_lrs] * len(groups)
             for lr, g in zip(swa_lrs, groups):
                 g['initial_lr'] = lr
-            self.lr_scheduler = SWALR(self.optimizer, swa_lr=swa_lrs, anneal_epochs=self._annealing_epochs,
-                                      anneal_strategy=self._annealing_strategy,
-                                      last_epoch=self._max_epochs if self._annealing_strategy == 'cos' else -1)
+            self.lr_scheduler = self._new_swalr(swa_lrs)
             self.n_averaged = 0
         if self.swa_start <= epoch <= self.swa_end:
             self._update_average()
@@ -159,6 +157,70 @@ class StochasticWeightAveraging:
                 m.momentum = momentum
         elif self._epoch == self.swa_end:
             self._transfer()
+
+    def _new_swalr(self, swa_lrs):
+        return SWALR(self.optimizer, swa_lr=swa_lrs, anneal_epochs=self._annealing_epochs,
+                     anneal_strategy=self._annealing_strategy,
+                     last_epoch=self._max_epochs if self._annealing_strategy == 'cos' else -1)
+
+    def state_dict(self):
+        """Taken at an epoch boundary, after on_train_epoch_end: the average as {parameter name: CPU tensor} (independent of
+        the bucket's layout; None before the first update), n_averaged, the last epoch, and the active epoch scheduler as
+        {'kind': 'plateau' | 'swalr' | None, 'state': its state_dict()}."""
+        sd = self.host_state()
+        if self.n_averaged > 0:
+            sd['average'] = self.average_dict(self.average.detach().cpu())
+        return sd
+
+    def host_state(self):
+        """state_dict() without the average: host values only, no device read (checkpoint.CheckpointWriter takes the average
+        from its snapshot and adds it with average_dict)."""
+        import copy
+        sch = self.lr_scheduler
+        kind = None if sch is None else 'plateau' if isinstance(sch, ReduceLROnPlateau) else 'swalr'
+        return {'average': None, 'n_averaged': int(self.n_averaged), 'epoch': self._epoch,
+                'scheduler': {'kind': kind, 'state': None if sch is None else copy.deepcopy(sch.state_dict())}}
+
+    def average_dict(self, host_flat):
+        """{parameter name: tensor} from a CPU image of the average in the bucket's layout."""
+        b = self.bucket
+        return {n: host_flat[o:o + p.numel()].clone().view(p.shape) for n, o, p in zip(b.names, b.offsets, b.params)}
+
+    def load_state_dict(self, sd):
+        """In place (the average keeps its address).  A stored SWALR is rebuilt with the arguments on_train_epoch_start uses —
+        the rates the optimizer's group holds, restored before this by TrainStep.load_state_dict — and then loaded; a stored
+        plateau state is loaded into the caller's plateau scheduler."""
+        b = self.bucket
+        self.n_averaged = int(sd['n_averaged'])
+        self._epoch = sd.get('epoch')
+        with torch.no_grad():
+            if sd.get('average') is None:
+                self.average.zero_()
+            else:
+                missing = [n for n in b.names if n not in sd['average']]
+                if missing:
+                    raise ValueError(f'StochasticWeightAveraging.load_state_dict: the average lacks {missing[:3]} ... ({len(missing)})')
+                host = torch.zeros(b.numel, dtype=self.average.dtype)
+                for n, o, p in zip(b.names, b.offsets, b.params):
+                    host[o:o + p.numel()].copy_(sd['average'][n].reshape(-1))
+                self.average.copy_(host)
+        kind, state = sd['scheduler']['kind'], sd['scheduler']['state']
+        if kind == 'swalr':
+            groups = self.optimizer.param_groups
+            for g in groups:
+                g.setdefault('initial_lr', g['lr'])
+            rates = [g['lr'] for g in groups]
+            self.lr_scheduler = self._new_swalr([float(g.get('swa_lr', g['lr'])) for g in groups])
+            self.lr_scheduler.load_state_dict(state)
+            for g, lr in zip(groups, rates):                # (the constructor's initial step rewrote the groups' rate)
+                g['lr'] = lr
+        elif kind == 'plateau':
+            if not isinstance(self.lr_scheduler, ReduceLROnPlateau):
+                raise ValueError('StochasticWeightAveraging.load_state_dict: the state holds a plateau scheduler; construct with '
+                                 'lr_scheduler=plateau_scheduler(step.optimizer)')
+            self.lr_scheduler.load_state_dict(state)
+        else:
+            self.lr_scheduler = None
 
     def _update_average(self):
         flat = self.bucket.flat

@@ -742,6 +742,26 @@ int dcs_adam_amsgrad_step_sumsq(float* p, const float* g, float* m, float* v, fl
  * epoch, outside any graph: n_averaged is passed by value. */
 int dcs_swa_average_f32(float* avg, const float* p, long n, long n_averaged, dcs_stream_t stream);
 
+/* Checkpoint snapshot: n tensors gathered bit for bit into one staging slab in ONE launch, so that the state a graph replay
+ * rewrites (parameters, moments, the SWA average, running statistics, device counters) is imaged between two replays without
+ * stopping the stream.  A word is 4 bytes.  items / first_block are DEVICE tables, built once (the sources' addresses are
+ * stable): item i copies `words` words from src (4-byte aligned) to dst + 4 dst_word; first_block long[n + 1] is the
+ * cumulative workgroup count, item i owning ceil(words / DCS_SNAPSHOT_BLOCK_WORDS) workgroups (none for words == 0).  A
+ * workgroup finds its item by bisection of first_block; 16-byte loads where src is 16-byte aligned, 4-byte loads otherwise,
+ * 16-byte stores, a scalar tail for words % 4; a fixed grid of DCS_SNAPSHOT_GRID workgroups strides over the rest.
+ * nonfinite int[n]: zeroed by the call on the same stream, then nonfinite[i] = the number of words of item i whose exponent
+ * bits are all ones (NaN, +-Inf) when is_f32 is set, 0 otherwise — integer atomics, one per wave: order-independent.
+ * The host checks, without reading the tables: null pointers, n outside 1..1024, dst_words < 0, dst not 16-byte aligned ->
+ * DCS_ERR_BADARG before any launch.  The tables live on the device, so the per-item rules — words >= 0, dst_word >= 0 and a
+ * multiple of 4, dst_word + words <= dst_words — are enforced where they can be read: the kernel copies NOTHING of an item
+ * that breaks one and reports nonfinite[i] = -1 (dcsnet.ops.snapshot_table refuses such an item on the host, before a table
+ * exists).  No host synchronisation, no host read, no allocation: legal between two graph replays and under capture. */
+#define DCS_SNAPSHOT_BLOCK_WORDS 1024
+#define DCS_SNAPSHOT_GRID 2048
+typedef struct { const void* src; long words; long dst_word; int is_f32; int pad_; } dcs_snapshot_item;
+int dcs_snapshot_words(const dcs_snapshot_item* items, int n, const long* first_block, void* dst, long dst_words,
+                       int* nonfinite, dcs_stream_t stream);
+
 /* The NaN-loss guard of c_network.py:257-261 without a host round trip.
  * dcs_step_guard:   *skip = isnan(*loss) ? 1 : 0.  `skip` is meant to be one extra element of the flat gradient
  *                   bucket, so that a data-parallel sum-all-reduce turns it into "some rank saw a NaN" and every

@@ -1,0 +1,89 @@
+"""Train DCS-Net / DR-Net on a directory of clean / noisy WAV pairs, with checkpoints (dcsnet/fit.py).
+
+    python tools/train.py dcs --clean-dir clean/ --noisy-dir noisy/ --out runs/dcs
+    python tools/train.py dcs --clean-dir clean/ --noisy-dir noisy/ --out runs/dcs --resume auto      (continue a stopped run)
+    python tools/train.py drs --clean-dir clean/ --noisy-dir noisy/ --out runs/drs --epochs 200 --batch 32
+
+The mode comes first, as in the reference's `train.py dcs 0`: the model code reads it from sys.argv[1].  Files are paired by
+name (mono 16-bit PCM at config.file_sr).  The train / validation split follows the reference's data.py: a seeded shuffle of
+the sorted file names, --val-split percent (80) for training; it is written to OUT/partition.json and reused on resume.
+OUT receives last.ckpt after every epoch, best.ckpt when the monitored value improved, metrics.jsonl, and final.ckpt — the SWA
+weights, the file tools/enhance.py and tools/evaluate.py should load — after the last epoch."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'dcs-net_amd'))
+
+MODES = ('dcs', 'drs', 'dc', 'dr')
+
+
+def partition(clean_dir, noisy_dir, out_dir, val_split, seed):
+    path = os.path.join(out_dir, 'partition.json')
+    if os.path.exists(path):
+        with open(path) as f:
+            return json.load(f)
+    import numpy as np
+    names = sorted(f for f in os.listdir(noisy_dir) if f.lower().endswith('.wav'))
+    if not names:
+        raise SystemExit(f'{noisy_dir}: no .wav files')
+    missing = [f for f in names if not os.path.isfile(os.path.join(clean_dir, f))]
+    if missing:
+        raise SystemExit(f'{clean_dir}: no clean file for {missing[0]}' + (f' and {len(missing) - 1} more' if missing[1:] else ''))
+    order = np.array(names)
+    np.random.RandomState(seed).shuffle(order)
+    cut = round(len(order) * (val_split / 100))
+    part = {'train': order[:cut].tolist(), 'validation': order[cut:].tolist()}
+    if not part['train'] or not part['validation']:
+        raise SystemExit(f'{len(names)} files split {val_split} / {100 - val_split} leave an empty set')
+    with open(path, 'w') as f:
+        json.dump(part, f)
+    return part
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('mode', choices=MODES, help='dcs / dc: DCS-Net (C_NETWORK); drs / dr: DR-Net (R_NETWORK)')
+    ap.add_argument('--clean-dir', required=True)
+    ap.add_argument('--noisy-dir', required=True)
+    ap.add_argument('--out', required=True, help='the run directory')
+    ap.add_argument('--epochs', type=int, default=None, help='default: config.max_epochs')
+    ap.add_argument('--batch', type=int, default=None, help='default: config.batch_size')
+    ap.add_argument('--resume', default=None, help="'auto' (OUT/last.ckpt when it exists) or a checkpoint path")
+    ap.add_argument('--val-split', type=float, default=80.0, help='percent of the files that train')
+    ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='activation storage (bf16: bf16 MFMA operands)')
+    ap.add_argument('--no-graph', action='store_true')
+    ap.add_argument('--device', default='cuda:0')
+    a = ap.parse_args()
+    if sys.argv[1] != a.mode:
+        ap.error('the mode must be the first argument (the model code reads sys.argv[1])')
+    real = a.mode in ('drs', 'dr')
+    if real and a.dtype == 'bf16':
+        ap.error(f'--dtype bf16 with {a.mode}: the real network has no bf16 activation storage')
+    import torch
+    from dcsnet.audio_store import DeviceAudioStore
+    from dcsnet.config import config, hparams
+    from dcsnet.fit import fit
+    if real:
+        from dcsnet.r_network import R_NETWORK as Net
+    else:
+        from dcsnet.c_network import C_NETWORK as Net
+    os.makedirs(a.out, exist_ok=True)
+    part = partition(a.clean_dir, a.noisy_dir, a.out, a.val_split, config.seed)
+    dev = torch.device(a.device)
+    stores = [DeviceAudioStore.from_wav([os.path.join(a.clean_dir, f) for f in part[k]],
+                                        [os.path.join(a.noisy_dir, f) for f in part[k]], config, dev, ids=part[k])
+              for k in ('train', 'validation')]
+    net = Net(config, dict(hparams), config.seed).to(dev)
+    if a.dtype == 'bf16':
+        net.set_activation_dtype('bf16')
+    out = fit(net, stores[0], stores[1], a.out, a.epochs or config.max_epochs, a.batch or hparams['batch_size'],
+              use_graph=not a.no_graph, resume=a.resume)
+    print(json.dumps({k: v for k, v in out.items() if k not in ('step', 'swa')}))
+
+
+if __name__ == '__main__':
+    main()
