@@ -3,7 +3,7 @@
 // reference's SiSNR (network_functions.py:30-42) per recording.  What stoi.hip's kernels do to one row, these do to one
 // recording, through the same device functions (stoi_common.h): a recording's score is bit-equal to dcs_stoi_f32 with B = 1.
 //
-//   ragged_prefix_kernel          one workgroup: out[i] = sum over j < i of v_j, v_j = the resampled length ceil(L_j up / down) or the
+//   ragged_prefix_kernel          (ragged_common.h, shared with frame_measures.hip) one workgroup: out[i] = sum over j < i of v_j, v_j = the resampled length ceil(L_j up / down) or the
 //                                   frame count of recording j, clamped to the capacity the host sized the buffers for — the
 //                                   later kernels take every per-recording size from the differences of this table, so no
 //                                   value in offsets[] makes them write outside their buffers
@@ -26,25 +26,16 @@
 //
 // Grids are sized from host integers (n, total, the longest recording); everything per recording is read from the offsets on the
 // device.  No atomics, no cross-workgroup synchronisation, no host read-back: capturable, bit-reproducible.
+#include "ragged_common.h"
 #include "stoi_common.h"
 
 namespace {
 
 using namespace dcs_stoi;
+using namespace dcs_ragged;                                  // rec_span, ragged_prefix_kernel, block_sum, bad_ragged
 
-constexpr int kMaxRecordings = 32767;                        // 2 n workgroup rows of the band kernel's grid
-constexpr long kMaxTotal = 1L << 40;
 constexpr int kMaxRatio = 1 << 16;                           // up, down: total * up and n_out * down stay inside int64
 constexpr double kSisnrEps = 1e-8;                           // SiSNR.__call__'s default, network_functions.py:31
-
-// recording i of offsets[n + 1], clamped into the buffer [0, total): first sample and length (0 for offsets that do not rise)
-__device__ __forceinline__ long rec_span(const long* __restrict__ offsets, long i, long total, long* first) {
-    long a = offsets[i], b = offsets[i + 1];
-    a = a < 0 ? 0 : (a > total ? total : a);
-    b = b < 0 ? 0 : (b > total ? total : b);
-    *first = a;
-    return b > a ? b - a : 0;
-}
 
 struct PrefixResample {                                       // v = ceil(L up / down)
     long up, down;
@@ -54,32 +45,6 @@ struct PrefixFrames {                                         // v = STOI frames
     long max_len;
     __device__ __forceinline__ long operator()(long L) const { return stoi_frames(L < max_len ? L : max_len); }
 };
-
-// out long[n + 1]: the exclusive prefix sums of v(L_i), each clamped to cap (integers: the order of the additions is immaterial)
-template <typename V>
-__global__ __launch_bounds__(256) void ragged_prefix_kernel(const long* __restrict__ offsets, int n, long total, V v, long cap,
-                                                            long* __restrict__ out) {
-    __shared__ long scan[256];
-    const int t = threadIdx.x;
-    const int chunk = (n + 255) / 256;
-    const int a = min(t * chunk, n), b = min(a + chunk, n);
-    long first, s = 0;
-    for (int i = a; i < b; ++i) s += v(rec_span(offsets, i, total, &first));
-    scan[t] = s;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const long add = t >= off ? scan[t - off] : 0;
-        __syncthreads();
-        scan[t] += add;
-        __syncthreads();
-    }
-    long run = scan[t] - s;
-    for (int i = a; i < b; ++i) {
-        out[i] = run < cap ? run : cap;
-        run += v(rec_span(offsets, i, total, &first));
-    }
-    if (t == 255) out[n] = scan[255] < cap ? scan[255] : cap;
-}
 
 // x float[total] (ragged) -> y float[y_off[n]] (ragged); y_off from ragged_prefix_kernel<PrefixResample>
 __global__ __launch_bounds__(256) void resample_poly_ragged_kernel(const float* __restrict__ x, const long* __restrict__ offsets, int n,
@@ -152,19 +117,6 @@ __global__ __launch_bounds__(256) void stoi_score_ext_ragged_kernel(const float*
     score_frames_both(X, X + Fcap * kBands, kept[b], red, out_d ? out_d + b : nullptr, out_e ? out_e + b : nullptr);
 }
 
-// every thread returns the sum of v over the workgroup; additions in a fixed order (red: LDS double[256])
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int t = threadIdx.x;
-    __syncthreads();                                         // red may still be read from the previous sum
-    red[t] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // SiSNR.__call__ per recording, without its batch mean: dot = <est, clean>, norm = <clean, clean>, s_target = dot clean /
 // (norm + eps), e_noise = est - s_target (per element), out = 10 log10(|s_target|^2 / (|e_noise|^2 + eps) + eps)
 __global__ __launch_bounds__(256) void sisnr_ragged_kernel(const float* __restrict__ clean, const float* __restrict__ est,
@@ -208,10 +160,6 @@ inline RaggedLayout ragged_layout(long n, long total) {
     s.off_band = s.off_idx + align256(s.Fcap * (long)sizeof(int));
     s.bytes = s.off_band + align256(2 * s.Fcap * kBands * (long)sizeof(float));
     return s;
-}
-
-inline bool bad_ragged(const long* offsets, int n, long total) {
-    return !offsets || n <= 0 || n > kMaxRecordings || total < 0 || total > kMaxTotal;
 }
 
 inline bool bad_stoi_ragged(const float* clean10, const float* est10, const long* offsets, int n, long total10, long longest10,

@@ -1,4 +1,5 @@
-"""How good is an enhanced recording: STOI and SI-SNR of whole recordings, scored where the Enhancer leaves them.
+"""How good is an enhanced recording: STOI, SI-SNR and (on request) ESTOI, segmental SNR, LLR and cepstrum distance of whole
+recordings, scored where the Enhancer leaves them.
 
     scorer = RecordingScorer(Enhancer(net, mode='dcs'))          (or a MagnitudeEnhancer)
     scores = scorer.score(noisy_waves, clean_waves, sample_rate=48000)
@@ -8,14 +9,17 @@
     scores = scorer.score_files(noisy_paths, clean_paths)         mono 16-bit PCM WAV of one rate
     scorer = RecordingScorer(enhancer, extended=True)             the dict gains 'estoi', 'estoi_noisy': the extended STOI
         (ESTOI, metrics.stoi(..., extended=True)), from the same two STOI calls: each makes both scores in one pass
+    scorer.frame_measures = True                                  the dict gains 'ssnr', 'llr', 'cd' and their _noisy twins:
+        segmental SNR (dB), LPC log-likelihood ratio and LPC cepstrum distance (Hu & Loizou; metrics.frame_measures), at
+        config.sr, from two more calls (metrics.frame_measures_ragged, csrc/frame_measures.hip)
 
 The Enhancer keeps everything ragged in one flat device buffer with an int64 offset table; the metrics speak the same
 convention (metrics.stoi_ragged / sisnr_ragged, csrc/stoi_ragged.hip), so a whole test set is scored in a handful of launches
 and nothing returns to the host before the caller asks for values.  Per call: enhancer.enhance_segments and stitch make the
 flat speech estimate; the clean recordings go through the same upload and the same ops.resample_sinc into a store of the
 scorer's own, at the plan's offsets; the estimate and the enhancer's resident (resampled) noisy signal are scored against it.
-summarise() takes its columns from the dict it is given.  PESQ, segmental SNR and the composite measures are not computed
-(DESIGN.md §7)."""
+summarise() takes its columns from the dict it is given.  PESQ, WSS and the composite measures (CSIG / CBAK / COVL) are not
+computed."""
 import numpy as np
 import torch
 
@@ -26,18 +30,26 @@ from .enhance import Enhancer, read_pcm16
 
 class RecordingScorer:
     """enhancer: an Enhancer or a MagnitudeEnhancer, used as it is configured (mode, segment geometry, graph).  extended: score
-    ESTOI as well; self.metrics names the dict's keys, METRICS or METRICS + EXTENDED."""
+    ESTOI as well.  The attribute frame_measures (default False; the constructor keeps its two arguments): score segmental SNR,
+    LLR and cepstrum distance as well.  self.metrics names the dict's keys: METRICS, then EXTENDED, then FRAME_MEASURES where
+    asked for."""
 
     METRICS = ('stoi', 'stoi_noisy', 'sisnr', 'sisnr_noisy')
     EXTENDED = ('estoi', 'estoi_noisy')
+    FRAME_MEASURES = ('ssnr', 'ssnr_noisy', 'llr', 'llr_noisy', 'cd', 'cd_noisy')
 
     def __init__(self, enhancer, extended=False):
         if not isinstance(enhancer, Enhancer):
             raise TypeError(f'RecordingScorer: expected an Enhancer or a MagnitudeEnhancer, got {type(enhancer).__name__}')
         self.enhancer = enhancer
         self.extended = bool(extended)
-        self.metrics = self.METRICS + self.EXTENDED if self.extended else self.METRICS
+        self.frame_measures = False                          # set it to True on the scorer: the constructor's arguments are pinned
         self._clean = None                                   # the clean recordings at config.sr, capacity kept across calls
+
+    @property
+    def metrics(self):
+        return (self.METRICS + (self.EXTENDED if self.extended else ()) +
+                (self.FRAME_MEASURES if self.frame_measures else ()))
 
     @staticmethod
     def _check_pairs(noisy_waves, clean_waves):
@@ -79,6 +91,11 @@ class RecordingScorer:
                   'sisnr_noisy': metrics.sisnr_ragged(clean, noisy, offsets)}
         if self.extended:
             scores['estoi'], scores['estoi_noisy'] = estoi, estoi_noisy
+        if self.frame_measures:
+            enhanced = metrics.frame_measures_ragged(clean, speech, offsets, enh.sr, longest=longest)
+            unprocessed = metrics.frame_measures_ragged(clean, noisy, offsets, enh.sr, longest=longest)
+            for k in ('ssnr', 'llr', 'cd'):                  # the order of FRAME_MEASURES
+                scores[k], scores[k + '_noisy'] = enhanced[k], unprocessed[k]
         if return_audio:
             return scores, enh._split(plan, speech)
         return scores
@@ -97,11 +114,17 @@ def summarise(scores):
     """Host summary of score()'s dict (the one device-to-host transfer): per metric the mean over the recordings that are not
     NaN and the count of those that are (calc_metric's convention), and the two mean improvements over the pairs where both
     sides are numbers.  -> (summary dict, per-recording float32 array [n, 4] in METRICS order).  With the extended keys in
-    the dict ('estoi', 'estoi_noisy'): their columns behind the four, [n, 6], and estoi_improvement in the summary."""
+    the dict ('estoi', 'estoi_noisy'): their columns behind the four, [n, 6], and estoi_improvement in the summary.  With the
+    frame-measure keys in the dict (RecordingScorer.FRAME_MEASURES): their six columns behind those, and ssnr_improvement
+    (enhanced - noisy, as for the others), llr_improvement and cd_improvement — these two are noisy - enhanced, because a
+    lower LLR or cepstrum distance is the better one, so a positive improvement always means the network helped."""
     keys = RecordingScorer.METRICS
     extended = all(k in scores for k in RecordingScorer.EXTENDED)
     if extended:
         keys = keys + RecordingScorer.EXTENDED
+    measures = all(k in scores for k in RecordingScorer.FRAME_MEASURES)
+    if measures:
+        keys = keys + RecordingScorer.FRAME_MEASURES
     table = torch.stack([scores[k].to(torch.float32) for k in keys], dim=1).cpu().numpy()
 
     def mean(v):
@@ -116,4 +139,9 @@ def summarise(scores):
     out['sisnr_improvement'] = mean(table[:, 2] - table[:, 3])
     if extended:
         out['estoi_improvement'] = mean(table[:, 4] - table[:, 5])
+    if measures:
+        j = keys.index('ssnr')
+        out['ssnr_improvement'] = mean(table[:, j] - table[:, j + 1])
+        out['llr_improvement'] = mean(table[:, j + 3] - table[:, j + 2])
+        out['cd_improvement'] = mean(table[:, j + 5] - table[:, j + 4])
     return out, table

@@ -30,6 +30,18 @@ with an int64 offset table (what dcsnet/enhance.py returns; csrc/stoi_ragged.hip
 that recording alone, resp. the reference's SiSNR (network_functions.py:30-42) in fp64 without its batch mean.
 dcsnet/evaluate.py builds the scorer of enhanced recordings on them.
 
+Segmental SNR, LLR, cepstrum distance.  `frame_measures()` below restates the three frame-based objective measures of
+Y. Hu, P. C. Loizou, "Evaluation of Objective Quality Measures for Speech Enhancement", IEEE TASLP 16(1), 2008, that are
+defined by formulae alone, after their published `comp_snr.m` / `comp_llr.m` / `comp_cep.m` (30 ms frames at 75 % overlap with
+the published frame count, a Hann-shaped window, segmental SNR clamped to [-10, 35] dB and averaged over all frames; order-16
+(order-10 below 10 kHz) LPC by the published Levinson-Durbin recursion, LLR clamped to [0, 2], LPC-cepstrum distance clamped
+to [0, 10], each averaged over the 95 % smallest frame values), at the signals' own rate.  It is host-side numpy in fp64.
+PARITY UNPINNED: neither pysepm nor the MATLAB originals are here to compare with; the tests check the defining properties and
+independent routes only (tests/test_frame_measures_cpu.py).  On the device it is `frame_measures_ragged()`
+(csrc/frame_measures.hip: fp64 until the final rounding; `frame_measures()` is its numerics contract,
+tests/test_frame_measures_device.py).  WSS and the composite measures (CSIG / CBAK / COVL) are not restated: the composites
+need PESQ, and WSS a filter-bank table that nothing here can verify.
+
 PESQ.  ITU-T P.862 is ~2 k lines of reference C with psychoacoustic tables; it is not restated.  `pesq` stays the
 imported package when present, else None (calc_metric then reports NaN, as in round 1)."""
 import numpy as np
@@ -295,3 +307,163 @@ def sisnr_ragged(clean, estimate, offsets):
     from . import ops
     clean, estimate, offsets, _ = _ragged_args('sisnr_ragged', clean, estimate, offsets, None)
     return ops.sisnr_ragged(clean, estimate, offsets)
+
+
+# ---- segmental SNR, LLR, cepstrum distance (Hu & Loizou) -------------------------------------------------------------------
+
+SSNR_RANGE = (-10.0, 35.0)      # dB, per frame
+LLR_RANGE = (0.0, 2.0)
+CD_RANGE = (0.0, 10.0)
+TRIM = 0.95                     # the share of the smallest frame values that LLR and CD average
+
+
+def frame_geometry(fs):
+    """(N, S, P) at rate fs: the frame length round(0.03 fs) (in integers, halves up), the hop N // 4 and the LPC order."""
+    fs = int(fs)
+    if fs <= 0:
+        raise ValueError(f'frame_geometry: fs={fs}')
+    N = (3 * fs + 50) // 100
+    return N, N // 4, 16 if fs >= 10000 else 10
+
+
+def frame_count(L, fs):
+    """The published frame count (it leaves out the last full frame): (L - N) // S for L >= N + S, else 0."""
+    N, S, _ = frame_geometry(fs)
+    return (L - N) // S if L >= N + S else 0
+
+
+def _measure_window(N):
+    return 0.5 * (1.0 - np.cos(2.0 * np.pi * (np.arange(N) + 1.0) / (N + 1.0)))
+
+
+def trimmed_count(V):
+    """K = max(1, floor(0.95 V + 0.5)) for V valid frames, in integers (0.95 V + 0.5 = (19 V + 10) / 20 exactly)."""
+    return max(1, (19 * int(V) + 10) // 20)
+
+
+def _trimmed_mean(values):
+    """The mean of the trimmed_count(V) smallest of V values; NaN for none."""
+    values = np.asarray(values, dtype=np.float64)
+    if values.size == 0:
+        return float('nan')
+    return float(np.mean(np.sort(values)[:trimmed_count(values.size)]))
+
+
+def _lpc(R, P):
+    """The published lpcoeff on autocorrelations R [..., P + 1] -> (A [..., P + 1] = [1, -a], E [..., P + 1] the prediction
+    error energies E_0 = R[0] .. E_P).  Rows whose E reaches 0 carry inf / NaN: the caller's validity test drops them."""
+    R = np.asarray(R, dtype=np.float64)
+    lead = R.shape[:-1]
+    E = np.empty(lead + (P + 1,))
+    E[..., 0] = R[..., 0]
+    a = np.zeros(lead + (P,))
+    with np.errstate(all='ignore'):
+        for i in range(P):
+            prev = a.copy()
+            k = (R[..., i + 1] - np.sum(prev[..., :i] * R[..., i:0:-1], axis=-1)) / E[..., i]
+            a[..., i] = k
+            if i:
+                a[..., :i] = prev[..., :i] - k[..., None] * prev[..., i - 1::-1]
+            E[..., i + 1] = (1.0 - k * k) * E[..., i]
+    return np.concatenate([np.ones(lead + (1,)), -a], axis=-1), E
+
+
+def _lpc_cepstrum(A):
+    """LPC cepstrum c [..., P + 1] (c[0] = 0, unused) of 1 / A(z), A [..., P + 1] with A[0] = 1."""
+    A = np.asarray(A, dtype=np.float64)
+    P = A.shape[-1] - 1
+    c = np.zeros_like(A)
+    with np.errstate(all='ignore'):
+        c[..., 1] = -A[..., 1]
+        for k in range(2, P + 1):
+            i = np.arange(1, k)
+            c[..., k] = -(A[..., k] + np.sum(i * c[..., 1:k] * A[..., k - 1:0:-1], axis=-1) / k)
+    return c
+
+
+def _autocorrelation(frames, P):
+    """R[..., k] = sum_{n = 0}^{N - 1 - k} f[n] f[n + k], k = 0 .. P, of frames [F, N]."""
+    N = frames.shape[1]
+    return np.stack([np.sum(frames[:, :N - k] * frames[:, k:], axis=1) for k in range(P + 1)], axis=1)
+
+
+def frame_values(x, y, fs):
+    """The per-frame values of the clean signal x and the estimate y (1-D, equal length) at rate fs: (ssnr [F], llr [F], cd [F],
+    valid bool [F]), clamped; llr and cd are meaningful where valid (both signals: R[0] > 0 and every E_i > 0)."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if x.shape != y.shape or x.ndim != 1:
+        raise ValueError(f'frame_measures: x {x.shape} and y {y.shape} must be 1-D signals of equal length')
+    N, S, P = frame_geometry(fs)
+    F = frame_count(len(x), fs)
+    if F == 0:
+        return np.zeros(0), np.zeros(0), np.zeros(0), np.zeros(0, dtype=bool)
+    w = _measure_window(N)
+    idx = S * np.arange(F)[:, None] + np.arange(N)[None, :]
+    xw, yw = x[idx] * w, y[idx] * w
+    with np.errstate(all='ignore'):
+        se, ne = np.sum(xw * xw, axis=1), np.sum((xw - yw) ** 2, axis=1)
+        ssnr = np.clip(10.0 * np.log10(se / (ne + EPS) + EPS), *SSNR_RANGE)
+        Rx, Ry = _autocorrelation(xw, P), _autocorrelation(yw, P)
+        (Ax, Ex), (Ay, Ey) = _lpc(Rx, P), _lpc(Ry, P)
+        valid = np.all(Ex > 0, axis=1) & np.all(Ey > 0, axis=1)
+        T = Rx[:, np.abs(np.arange(P + 1)[:, None] - np.arange(P + 1)[None, :])]           # [F, P + 1, P + 1]
+        num, den = np.einsum('fi,fij,fj->f', Ay, T, Ay), np.einsum('fi,fij,fj->f', Ax, T, Ax)
+        llr = np.clip(np.log(num / den), *LLR_RANGE)
+        cx, cy = _lpc_cepstrum(Ax), _lpc_cepstrum(Ay)
+        cd = np.clip(10.0 / np.log(10.0) * np.sqrt(2.0 * np.sum((cx[:, 1:] - cy[:, 1:]) ** 2, axis=1)), *CD_RANGE)
+    return ssnr, llr, cd, valid
+
+
+def frame_measures(x, y, fs):
+    """Segmental SNR (dB), LPC log-likelihood ratio and LPC cepstrum distance of the estimate y against the clean signal x
+    (1-D, equal length, both at rate fs), after Hu & Loizou's comp_snr.m / comp_llr.m / comp_cep.m -> {'ssnr', 'llr', 'cd'} as
+    Python floats.  Frames of N = round(0.03 fs) samples at hop N // 4, the published count (L - N) // (N // 4) (0 below
+    N + N // 4 samples), window 0.5 (1 - cos(2 pi (i + 1) / (N + 1))).  ssnr: the mean over ALL frames of 10 log10(se / (ne +
+    EPS) + EPS) clamped to [-10, 35] (digital silence counts as -10, as published); NaN without a frame.  llr, cd: per frame
+    log(A_y T A_y' / A_x T A_x') clamped to [0, 2] and (10 / ln 10) sqrt(2 sum (c_x - c_y)^2) clamped to [0, 10] from the
+    order-P LPC models (P = 16 for fs >= 10000, else 10), over the frames where both recursions keep every error energy
+    positive; the score is the mean of the max(1, floor(0.95 V + 0.5)) smallest of those V values, NaN for V = 0.  PARITY
+    UNPINNED (see the module docstring): tests/test_frame_measures_cpu.py checks the defining properties and independent
+    routes."""
+    ssnr, llr, cd, valid = frame_values(x, y, fs)
+    return {'ssnr': float(np.mean(ssnr)) if len(ssnr) else float('nan'),
+            'llr': _trimmed_mean(llr[valid]), 'cd': _trimmed_mean(cd[valid])}
+
+
+def ssnr(x, y, fs):
+    """frame_measures(x, y, fs)['ssnr']."""
+    return frame_measures(x, y, fs)['ssnr']
+
+
+def llr(x, y, fs):
+    """frame_measures(x, y, fs)['llr']."""
+    return frame_measures(x, y, fs)['llr']
+
+
+def cepstrum_distance(x, y, fs):
+    """frame_measures(x, y, fs)['cd']."""
+    return frame_measures(x, y, fs)['cd']
+
+
+def measure_window(fs, device):
+    """_measure_window(N) of rate fs as float64 [N] on `device` (cached): the host function's own bits."""
+    N = frame_geometry(fs)[0]
+    key = ('measure_window', N, str(device))
+    t = _device_tables.get(key)
+    if t is None:
+        import torch
+        t = torch.from_numpy(_measure_window(N)).to(device)
+        _device_tables[key] = t
+    return t
+
+
+def frame_measures_ragged(clean, estimate, offsets, fs, longest=None):
+    """frame_measures(clean[a:b], estimate[a:b], fs) for every recording [a, b) = offsets[i:i + 2] of two flat device buffers ->
+    {'ssnr', 'llr', 'cd'}: float32 [n] device tensors (NaN where the host function has NaN), fp64 until that rounding, in three
+    launches whatever n is (csrc/frame_measures.hip) and without a host read-back (capturable when offsets are on the
+    device).  No resampling: the measures are taken at the signals' own rate fs, 8000 .. 48000 (DcsHipError otherwise).
+    offsets, longest: as for stoi_ragged (no grid here depends on longest).  CPU signals raise DcsHipError."""
+    from . import ops
+    clean, estimate, offsets, _ = _ragged_args('frame_measures_ragged', clean, estimate, offsets, longest)
+    s, l, c = ops.frame_measures_ragged(clean, estimate, offsets, fs)
+    return {'ssnr': s, 'llr': l, 'cd': c}

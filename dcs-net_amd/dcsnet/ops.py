@@ -1489,6 +1489,46 @@ def sisnr_ragged(clean, est, offsets):
     return out
 
 
+def frame_measures_workspace_bytes(n, total, fs):
+    """The workspace of frame_measures_ragged for n recordings of `total` samples together at rate fs (host arithmetic)."""
+    nbytes = _lib.load().dcs_frame_measures_ragged_workspace_bytes(int(n), int(total), int(fs))
+    if nbytes < 0:
+        raise _lib.DcsHipError(f'frame_measures_ragged: unsupported arguments ({n} recordings, {total} samples, fs={fs}; the rate '
+                               f'must lie in 8000 .. 48000)')
+    return nbytes
+
+
+def frame_measures_ragged(clean, est, offsets, fs, window=None, out=None, workspace=None):
+    """Segmental SNR, LPC log-likelihood ratio and LPC cepstrum distance of n recordings of different lengths at their own
+    rate fs (8000 .. 48000): clean / est float [total], offsets int64 [n + 1] on the device -> (ssnr, llr, cd), float [n] each,
+    metrics.frame_measures per recording with every sum in fp64 (dcs_frame_measures_ragged_f32: three launches whatever n is).
+    window: metrics.measure_window(fs, device) (the default).  out (three float32 [n] tensors) and workspace (uint8, at least
+    frame_measures_workspace_bytes) let a caller own the buffers the call writes."""
+    n, total = _chk_ragged('frame_measures_ragged', offsets, clean, est)
+    dev = clean.device
+    fs = int(fs)
+    nbytes = frame_measures_workspace_bytes(n, total, fs)
+    if window is None:
+        from .metrics import measure_window
+        window = measure_window(fs, dev)
+    if window.dtype != torch.float64 or window.dim() != 1 or not window.is_contiguous() or window.device != dev:
+        raise _lib.DcsHipError(f'frame_measures_ragged: window must be a contiguous float64 [N] tensor on {dev}')
+    if out is None:
+        out = tuple(torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+    for o in out:
+        _chk(o, 'frame_measures_ragged: out', 1)
+        if o.numel() != n or o.device != dev:
+            raise _lib.DcsHipError(f'frame_measures_ragged: out must be three float32 [{n}] tensors on {dev}')
+    ws = _workspace(nbytes, dev) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
+        raise _lib.DcsHipError(f'frame_measures_ragged: workspace must be a contiguous uint8 tensor on {dev}')
+    sig = (ptr(clean), ptr(est)) if total else (None, None)
+    check(_lib.load().dcs_frame_measures_ragged_f32(*sig, ptr(offsets), n, total, fs, ptr(window), window.numel(), ptr(out[0]),
+                                                    ptr(out[1]), ptr(out[2]), ptr(ws), ws.numel(), cur_stream()),
+          'dcs_frame_measures_ragged_f32')
+    return tuple(out)
+
+
 # ---- HBM-resident training audio (csrc/audio_store.hip, dcsnet/audio_store.py) ----------------------------------------
 
 _SINC_LOWPASS_WIDTH, _SINC_ROLLOFF = 6, 0.99                 # torchaudio 0.9.0's Resample defaults (config.py:61)

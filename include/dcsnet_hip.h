@@ -915,6 +915,25 @@ int dcs_sisnr_ragged_f32(const float* clean, const float* est, const long* offse
                          dcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Segmental SNR, LPC log-likelihood ratio and LPC cepstrum distance of whole recordings (Hu & Loizou's comp_snr / comp_llr /
+ * comp_cep as dcsnet/metrics.py::frame_measures restates them: that host function is the numerics contract),
+ * frame_measures.hip, in the ragged convention above (same limits on n and total, same clamping of the offsets), at the
+ * signals' own rate fs, 8000 <= fs <= 48000 (anything else: DCS_ERR_BADARG).  Frames of N = round(0.03 fs) samples at hop
+ * S = N / 4, F = (L - N) / S of them for L >= N + S, else 0; LPC order 16 for fs >= 10000, else 10.
+ * dcs_frame_measures_ragged_workspace_bytes: pure host arithmetic, frame base long[n + 1] | per-frame values double[3][Fc] |
+ *   validity int[Fc], Fc = total / S (it follows the total length); < 0 for bad arguments (Fc must stay below 2^31).
+ * dcs_frame_measures_ragged_f32: out_ssnr / out_llr / out_cd float[n]: the mean over all frames of the segmental SNR clamped to
+ *   [-10, 35] dB (NaN when F = 0); the means of the K = max(1, floor(0.95 V + 0.5)) smallest LLR (clamped to [0, 2]) and CD
+ *   (clamped to [0, 10]) values of the V valid frames (NaN when V = 0).  window double[window_len] on the device:
+ *   w[i] = 0.5 (1 - cos(2 pi (i + 1) / (N + 1))), window_len = N.  Every sum in fp64 in a fixed order, one rounding to float
+ *   at the end.  Three launches whatever n is; no atomics, no sync, no read-back (capturable, bit-reproducible); a
+ *   recording's scores do not depend on the other recordings of the call. */
+long dcs_frame_measures_ragged_workspace_bytes(int n, long total, int fs);
+int dcs_frame_measures_ragged_f32(const float* clean, const float* est, const long* offsets, int n, long total, int fs,
+                                  const double* window, int window_len, float* out_ssnr, float* out_llr, float* out_cd,
+                                  void* workspace, long workspace_bytes, dcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * HBM-resident training audio (data.py:68-143: resample, crop, noise = noisy - clean, three torch.stft calls per item on the
  * loader workers; dcsnet/audio_store.py), audio_store.hip.
  * dcs_resample_sinc_f32: torchaudio.transforms.Resample(orig * g, new_ * g) of torchaudio 0.9.0 (sinc_interpolation, lowpass

@@ -7,7 +7,9 @@ enhanced and of the unprocessed recordings against the clean ones, on the device
 Files are paired by name: every *.wav of noisy_dir needs its namesake in clean_dir, mono 16-bit PCM, one sample rate, each pair
 of one length.  Prints one JSON line: the file count, the mean of each metric over the files where it is a number (and how
 many were not), and the mean improvements stoi - stoi_noisy and sisnr - sisnr_noisy.  --csv writes the per-file table.
---extended adds the extended STOI (ESTOI: estoi, estoi_noisy, estoi_improvement) to the JSON line and the table."""
+--extended adds the extended STOI (ESTOI: estoi, estoi_noisy, estoi_improvement) to the JSON line and the table.
+--frame-measures adds segmental SNR, LPC log-likelihood ratio and LPC cepstrum distance (ssnr, llr, cd, their _noisy twins and
+ssnr_improvement, llr_improvement, cd_improvement; the last two are noisy - enhanced: lower is better)."""
 import argparse
 import json
 import os
@@ -41,6 +43,8 @@ def main():
                     help='dcs / drs: subtract the noise estimate; dc / dr: apply the mask (drs, dr: the real network, R_NETWORK)')
     ap.add_argument('--csv', default=None, help='write the per-file table here')
     ap.add_argument('--extended', action='store_true', help='score the extended STOI (ESTOI) as well')
+    ap.add_argument('--frame-measures', action='store_true',
+                    help='score segmental SNR, LLR and cepstrum distance (Hu & Loizou) as well')
     ap.add_argument('--segment-frames', type=int, default=2000)
     ap.add_argument('--overlap-frames', type=int, default=300)
     ap.add_argument('--batch-segments', type=int, default=16)
@@ -69,6 +73,7 @@ def main():
     enh = Enh(net, mode=a.mode, segment_frames=a.segment_frames, overlap_frames=a.overlap_frames,
               batch_segments=a.batch_segments, use_graph=not a.no_graph)
     scorer = RecordingScorer(enh, extended=a.extended)
+    scorer.frame_measures = a.frame_measures
     summary, table = summarise(scorer.score_files(noisy, clean))
     if a.csv:
         with open(a.csv, 'w') as f:

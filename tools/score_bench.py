@@ -12,11 +12,18 @@ Launch counts are the kernels each method issues per pass (from the entry points
 ESTOI from one pass of the resampling, keep and band kernels), and records its cost relative to the STOI-only ragged call.
 --parent-json takes the JSON this tool printed on another commit in the same session and records that commit's ragged pass.
 
-usage: python tools/score_bench.py [--out profiles/score_bench.json] [--recordings 32] [--extended] [--parent-json FILE]"""
+--frame-measures times another question instead: the device pass of metrics.frame_measures_ragged (segmental SNR, LLR, cepstrum
+distance; csrc/frame_measures.hip) on the same seeded set beside the STOI pass, the two alternating in the same rounds, plus
+the wall-clock time of the host function metrics.frame_measures over the set and the largest device - host differences ->
+profiles/frame_measures_bench.json.
+
+usage: python tools/score_bench.py [--out profiles/score_bench.json] [--recordings 32] [--extended] [--parent-json FILE]
+       python tools/score_bench.py --frame-measures [--out profiles/frame_measures_bench.json] [--recordings 32]"""
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -24,7 +31,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'dcs-net_amd'))
-from dcsnet import metrics  # noqa: E402
+from dcsnet import metrics, ops  # noqa: E402
 
 
 def synthetic_set(n, seed, rate=16000):
@@ -44,15 +51,83 @@ def synthetic_set(n, seed, rate=16000):
     return clean, est
 
 
+def timed_rounds(methods, min_seconds, rounds=3):
+    """{name: [seconds per pass]}: the methods alternate in rounds; in each a method repeats its pass (each pass timed by its own
+    event pair) until it has filled its share of min_seconds."""
+    times = {name: [] for name, _ in methods}
+    for r in range(rounds):
+        for name, fn in methods:
+            spent = 0.0
+            while spent < min_seconds / rounds:
+                s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                fn()
+                t.record()
+                t.synchronize()
+                times[name].append(s.elapsed_time(t) / 1e3)
+                spent += times[name][-1]
+        print(f'[score_bench] round {r + 1} of {rounds} done', file=sys.stderr, flush=True)
+    return times
+
+
+def pass_stats(times, n):
+    med = float(np.median(times))
+    return {'passes': len(times), 'timed_s': round(sum(times), 2), 'ms_per_pass_median': round(med * 1e3, 3),
+            'ms_per_pass_min': round(min(times) * 1e3, 3), 'recordings_per_s': round(n / med, 1)}
+
+
+def frame_measures_bench(a, c, e, off, off_h, longest, fs):
+    """The device pass of the three frame measures beside the STOI pass, and the host function on the same set."""
+    n = a.recordings
+    spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
+    methods = (('stoi_ragged_call', lambda: metrics.stoi_ragged(c, e, off, fs, longest=longest)),
+               ('frame_measures_ragged_call', lambda: metrics.frame_measures_ragged(c, e, off, fs, longest=longest)))
+    first = {}
+    for name, fn in methods:
+        first[name] = fn()
+        torch.cuda.synchronize()
+    times = timed_rounds(methods, a.min_seconds)
+    ch, eh = c.cpu().numpy(), e.cpu().numpy()
+    t0 = time.perf_counter()
+    host = [metrics.frame_measures(ch[p:q], eh[p:q], fs) for p, q in spans]
+    host_s = time.perf_counter() - t0
+    N, S, P = metrics.frame_geometry(fs)
+    res = {'metric': 'frame_measures_recordings', 'device': torch.cuda.get_device_name(0), 'recordings': n,
+           'audio_seconds': round(float(off_h[-1]) / fs, 2), 'lengths_s': '1 .. 10 s at 16 kHz, uniform, seeded',
+           'frames': int(sum(metrics.frame_count(q - p, fs) for p, q in spans)), 'frame': {'N': N, 'S': S, 'lpc_order': P},
+           'first_measurement': 'no earlier figure exists for this pass on the MI355X and nothing at the parent commit compares',
+           'timing': 'device events around one pass over the set; the two device methods alternate in 3 rounds, each filling a '
+                     'third of min_seconds with repeated passes; median over the passes.  host: wall clock of one loop of '
+                     'metrics.frame_measures over the set (numpy, fp64), signals already on the host',
+           'min_seconds': a.min_seconds,
+           'kernel_launches': {'frame_measures_ragged_call': 3, 'stoi_ragged_call': 2 * 2 + 4, 'stoi_ragged_call_fills': 2},
+           'workspace_bytes': int(ops.frame_measures_workspace_bytes(n, int(off_h[-1]), fs)),
+           'host_loop_s': round(host_s, 4)}
+    for name, _ in methods:
+        res[name] = pass_stats(times[name], n)
+    res['frame_measures_over_stoi_pass'] = round(res['frame_measures_ragged_call']['ms_per_pass_median'] /
+                                                 res['stoi_ragged_call']['ms_per_pass_median'], 3)
+    res['host_loop_over_device_pass'] = round(host_s * 1e3 / res['frame_measures_ragged_call']['ms_per_pass_median'], 1)
+    for k in ('ssnr', 'llr', 'cd'):
+        res[f'{k}_max_abs_diff_vs_host'] = float(np.nanmax(np.abs(first['frame_measures_ragged_call'][k].cpu().numpy() -
+                                                                  np.array([m[k] for m in host]))))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'score_bench.json'))
+    ap.add_argument('--out', default=None, help='default: profiles/score_bench.json (--frame-measures: '
+                                                'profiles/frame_measures_bench.json); - for none')
+    ap.add_argument('--frame-measures', action='store_true',
+                    help='time metrics.frame_measures_ragged beside the STOI pass and the host function instead')
     ap.add_argument('--recordings', type=int, default=32)
     ap.add_argument('--min-seconds', type=float, default=1.0)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--extended', action='store_true', help="time stoi_ragged(extended='both') beside the STOI-only call")
     ap.add_argument('--parent-json', default=None, help="this tool's JSON of the parent commit, same box, same session")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'frame_measures_bench.json' if a.frame_measures else 'score_bench.json')
     dev = torch.device('cuda:0')
     fs = 16000
     clean, est = synthetic_set(a.recordings, a.seed, fs)
@@ -63,6 +138,8 @@ def main():
     off = torch.from_numpy(off_h).to(dev)
     longest = int(np.diff(off_h).max())
     spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
+    if a.frame_measures:
+        return write_result(frame_measures_bench(a, c, e, off, off_h, longest, fs), a.out)
 
     def ragged():
         return metrics.stoi_ragged(c, e, off, fs, longest=longest)
@@ -84,22 +161,8 @@ def main():
         first[name] = fn()
         torch.cuda.synchronize()
         print(f'[score_bench] warm-up of {name} done', file=sys.stderr, flush=True)
-    # The methods differ by orders of magnitude per pass, so they alternate in ROUNDS: in each round every method repeats
-    # its pass (each pass timed by its own event pair) until it has filled its share of --min-seconds.
-    rounds = 3
-    times = {name: [] for name, _ in methods}
-    for r in range(rounds):
-        for name, fn in methods:
-            spent = 0.0
-            while spent < a.min_seconds / rounds:
-                s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s.record()
-                fn()
-                t.record()
-                t.synchronize()
-                times[name].append(s.elapsed_time(t) / 1e3)
-                spent += times[name][-1]
-        print(f'[score_bench] round {r + 1} of {rounds} done', file=sys.stderr, flush=True)
+    # The methods differ by orders of magnitude per pass, so they alternate in ROUNDS (timed_rounds).
+    times = timed_rounds(methods, a.min_seconds)
     sisnr = []
     for _ in range(20):
         s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -119,9 +182,7 @@ def main():
                                'host_loop_copies': 2 * n},
            'sisnr_ragged_us_median': round(float(np.median(sisnr)), 2)}
     for name, _ in methods:
-        med = float(np.median(times[name]))
-        res[name] = {'passes': len(times[name]), 'timed_s': round(sum(times[name]), 2), 'ms_per_pass_median': round(med * 1e3, 3),
-                     'ms_per_pass_min': round(min(times[name]) * 1e3, 3), 'recordings_per_s': round(n / med, 1)}
+        res[name] = pass_stats(times[name], n)
     for name in ('per_recording_stoi_batch', 'host_loop'):
         res[f'speedup_ragged_vs_{name}'] = round(res[name]['ms_per_pass_median'] / res['ragged_call']['ms_per_pass_median'], 2)
     if a.extended:
@@ -137,10 +198,14 @@ def main():
         res['parent_commit_ragged_call'] = parent['ragged_call']
         res['ragged_call_over_parent_commit'] = round(res['ragged_call']['ms_per_pass_median'] /
                                                       parent['ragged_call']['ms_per_pass_median'], 3)
+    write_result(res, a.out)
+
+
+def write_result(res, out):
     print(json.dumps(res))
-    if a.out != '-':
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
+    if out != '-':
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
             json.dump(res, f, indent=1)
 
 
