@@ -1,5 +1,6 @@
 // conv_common.h — geometry and the virtual-input gather shared by the direct (conv_direct.hip) and
-// MFMA implicit-GEMM (conv_mfma.hip) complex convolution kernels.
+// MFMA implicit-GEMM (conv_mfma.hip) complex convolution kernels, and the per-file launchers that the
+// entry points and their routing (conv_api.hip) choose among.
 #pragma once
 #include "dcs_common.h"
 
@@ -22,14 +23,14 @@
 #define dcs_conv_enc0_wgrad_ok dcs_conv_enc0_wgrad_ok_h
 #define dcs_conv_enc0_wgrad_launch dcs_conv_enc0_wgrad_launch_h
 #define dcs_conv_wgrad_mfma_ok dcs_conv_wgrad_mfma_ok_h
-#define dcs_conv_wgrad_mfma_slabs dcs_conv_wgrad_mfma_slabs_h
+#define dcs_conv_wgrad_mfma_plan dcs_conv_wgrad_mfma_plan_h
 #define dcs_conv_wgrad_mfma_launch dcs_conv_wgrad_mfma_launch_h
-#define dcs_conv_wgrad_mfma_planes_bytes dcs_conv_wgrad_mfma_planes_bytes_h
-#define dcs_conv_wgrad_fold_ok dcs_conv_wgrad_fold_ok_h
-#define dcs_conv_wgrad_fold_workspace_bytes dcs_conv_wgrad_fold_workspace_bytes_h
 #define dcs_conv_wgrad_fold_run dcs_conv_wgrad_fold_run_h
 #define dcs_conv_small_dgrad_ok dcs_conv_small_dgrad_ok_h
 #define dcs_conv_small_dgrad_launch dcs_conv_small_dgrad_launch_h
+#define dcs_conv_direct_launch dcs_conv_direct_launch_h
+#define dcs_conv_direct_wgrad_launch dcs_conv_direct_wgrad_launch_h
+#define dcs_upsample_cat_bwd_launch dcs_upsample_cat_bwd_launch_h
 #endif
 
 namespace conv {
@@ -48,6 +49,31 @@ struct Args {
     // atomics.  Forward launches with act = NONE and no coef only.
     float* stat;
     int stat_stride;
+};
+
+// The 14 integers every conv entry point takes: forward geometry of y = conv(upsample(cat(x1, x2)))
+struct Geom { int B, Hin, Win, C1, C2, up_f, up_t, Cout, kh, kw, sf, st, pad_f, pad_t; };
+inline bool geom_ok(const Geom& g) {
+    return g.B > 0 && g.Hin > 0 && g.Win > 0 && g.C1 > 0 && g.C2 >= 0 && g.Cout > 0 && g.up_f >= 1 && g.up_t >= 1 && g.kh >= 1 &&
+           g.kw >= 1 && g.sf >= 1 && g.st >= 1 && g.pad_f >= 0 && g.pad_t >= 0;
+}
+// the data gradient runs as a correlation with padding k - 1 - pad
+inline bool dgrad_pad_ok(const Geom& g) { return g.pad_f <= g.kh - 1 && g.pad_t <= g.kw - 1; }
+inline long align256(long n) { return (n + 255) / 256 * 256; }
+constexpr int kWgradMaxTaps = 52;      // weight gradients: kernels up to 7x7 (conv_direct.hip: 4 threads x 13 taps)
+
+// Workspace layout of a weight-gradient launch, written once for the query and the launch (the MFMA routes':
+// dcs_conv_wgrad_mfma_plan; the others': conv_api.hip's wgrad_plan, one class and no planes):
+//   [ slab_w float2[n_slabs][ncls][wsz] | slab_b float2[n_slabs][ncls][Cout] | pad to 256 | g_Y planes ]
+struct WgradLayout {
+    bool fold;                 // MFMA: per parity class at source resolution (3x3 over an upsampled input), else the plain form
+    int ncls, TH, TW;          // classes (1: plain) and the MFMA kernels' pixel tile
+    int n_slabs;               // partial slabs per class
+    long wsz;                  // float2 values of one slab's weight part: class taps x Cin x Cout
+    long slab_bytes;           // weight + bias slabs of all classes
+    long planes_off;           // align256(slab_bytes)
+    long planes_bytes;         // pre-split g_Y (three bf16 planes in A-fragment order) the emulated kernel can use, 0 if none
+    long bytes;                // planes_off + planes_bytes, or slab_bytes without planes
 };
 
 // One output-parity class of a decomposed convolution (conv_mfma.hip): its own sub-kernel, padding,
@@ -123,18 +149,16 @@ void stride_classes(int Cout, int Cin, int kh, int kw, int sf, int st, int pad_f
 
 // conv_wgrad_mfma.hip
 bool dcs_conv_wgrad_mfma_ok(int Cin, int Cout, int kh, int kw, int C1);
-int dcs_conv_wgrad_mfma_slabs(const conv::Args& a, int* TH, int* TW);
-int dcs_conv_wgrad_mfma_launch(conv::Args& a, const act_t* gy, float2* slab_w, float* slab_b, int n_slabs,
-                               hipStream_t stream, void* planes = nullptr);
-// bytes of the pre-split g_Y (three bf16 planes in A-fragment order) the emulated kernel of this geometry can use, 0 if none
-long dcs_conv_wgrad_mfma_planes_bytes(const conv::Args& a);
-
-// conv_wgrad_mfma.hip: weight gradient of a 3x3 conv over an upsampled input in its folded (per-class, source-
-// resolution) form; kernel + reduce into the parameter layout
-bool dcs_conv_wgrad_fold_ok(const conv::Args& a);
-long dcs_conv_wgrad_fold_workspace_bytes(const conv::Args& a);
-int dcs_conv_wgrad_fold_run(const conv::Args& a, const act_t* gy, void* workspace, long workspace_bytes, float* gw_r,
-                            float* gw_i, float* gb_r, float* gb_i, int transposed, hipStream_t stream);
+// route, tile, slab count and workspace layout of a forward geometry that passes dcs_conv_wgrad_mfma_ok (a.Hout / a.Wout set)
+conv::WgradLayout dcs_conv_wgrad_mfma_plan(const conv::Args& a);
+// plain route: the kernel alone.  slab_w / slab_b / planes: the plan's regions (planes: nullptr runs without the pre-split g_Y)
+int dcs_conv_wgrad_mfma_launch(conv::Args& a, const conv::WgradLayout& p, const act_t* gy, float2* slab_w, float* slab_b,
+                               void* planes, hipStream_t stream);
+// fold route: weight gradient of a 3x3 conv over an upsampled input in its folded (per-class, source-resolution) form;
+// kernel + reduce into the parameter layout
+int dcs_conv_wgrad_fold_run(const conv::Args& a, const conv::WgradLayout& p, const act_t* gy, float2* slab_w, float2* slab_b,
+                            void* planes, float* gw_r, float* gw_i, float* gb_r, float* gb_i, int transposed,
+                            hipStream_t stream);
 
 // conv_wgrad_small.hip (a: forward geometry with conv_direct.hip's 16x16 tiling filled in)
 bool dcs_conv_wgrad_small_ok(const conv::Args& a);
@@ -146,8 +170,20 @@ bool dcs_conv_small_dgrad_ok(int Cin, int Cout, int kh, int kw, int sf, int st, 
 int dcs_conv_small_dgrad_launch(const act_t* gy, const float* wp_bwd, act_t* gx, int B, int Hx, int Wx, int Hg, int Wg,
                                 int pad_f, int pad_t, hipStream_t stream);
 
-// conv_direct.hip: n small direct correlations (same batch, Cout 1 or 2) in one launch
+// conv_direct.hip: the direct (non-GEMM) kernels.  16x16 output tiles: conv_geometry fills a's tiling from Hout / Wout
+bool dcs_conv_geometry(conv::Args& a);
+int dcs_conv_direct_launch(conv::Args& a, hipStream_t stream);
+// n small direct correlations (same batch, Cout 1 or 2) in one launch
 int dcs_conv_direct_multi(conv::Args* a, int n, hipStream_t stream);
+// generic weight-gradient kernel (a: tiling filled in, at most conv::kWgradMaxTaps taps) + its slab reduce
+int dcs_conv_direct_wgrad_launch(const conv::Args& a, const act_t* gy, float2* slab_w, float2* slab_b, int n_slabs, float* gw_r,
+                                 float* gw_i, float* gb_r, float* gb_i, int transposed, hipStream_t stream);
+// sum the slabs and scatter into the reference's parameter layout (wgrad_reduce.hip: immediate, or deferred + batched)
+int dcs_conv_wgrad_reduce(const float2* slab_w, const float2* slab_b, int n_slabs, float* gw_r, float* gw_i, float* gb_r,
+                          float* gb_i, int Cout, int Cin, int kh, int kw, int transposed, hipStream_t stream);
+// block sum over the upsample factors and channel split of a virtual-input gradient
+int dcs_upsample_cat_bwd_launch(const act_t* gxv, act_t* gx1, act_t* gx2, int B, int Hin, int Win, int C1, int C2, int up_f,
+                                int up_t, hipStream_t stream);
 // conv_k7.hip: register-blocked 7x7 / stride 1 / pad 3 complex convs with (Cin, Cout) in {(2,1), (1,2), (1,1)}
 bool dcs_conv_k7_ok(const conv::Args* a, int n);
 int dcs_conv_k7_launch(const conv::Args* a, int n, hipStream_t stream);

@@ -534,8 +534,6 @@ int dcs_conv_enc0_launch(conv::Args a, hipStream_t stream) {
     return DCS_OK;
 }
 
-// Weight gradient (forward geometry `a`, x1 set): at most max_slabs partial slabs float2[49][8] (+ float2[8] bias) are
-// written, *n_used says how many; the caller reduces them (launch_wgrad_reduce of conv_direct.hip).
 int dcs_conv_enc0_stat_rows(const conv::Args& a0) {
     conv::Args a = a0;
     if (!enc0_geom(a)) return 0;
@@ -548,10 +546,12 @@ int dcs_conv_enc0_stat_rows(const conv::Args& a0) {
     return (int)(ntile < cus * 4 ? ntile : cus * 4);
 }
 
-bool dcs_conv_enc0_wgrad_ok(const conv::Args& a) { return enc0_geom(a) && a.x1; }
+// Weight gradient (forward geometry `a`, x1 set): at most max_slabs partial slabs float2[49][8] (+ float2[8] bias) are
+// written, *n_used says how many; the caller reduces them (dcs_conv_wgrad_reduce of conv_direct.hip).
+bool dcs_conv_enc0_wgrad_ok(const conv::Args& a) { return enc0_geom(a); }      // geometry only: workspace plans ask without operands
 int dcs_conv_enc0_wgrad_launch(conv::Args a, const act_t* gy, float2* slab_w, float2* slab_b, int max_slabs, int* n_used,
                                hipStream_t stream) {
-    if (!dcs_conv_enc0_wgrad_ok(a) || !gy || !slab_w || !slab_b || max_slabs < 1) return DCS_ERR_BADARG;
+    if (!dcs_conv_enc0_wgrad_ok(a) || !a.x1 || !gy || !slab_w || !slab_b || max_slabs < 1) return DCS_ERR_BADARG;
     a.Hout = (a.Hin + 2 * a.pad_f - K7) / 2 + 1;
     a.Wout = (a.Win + 2 * a.pad_t - K7) / 2 + 1;
     a.tiles_w = (a.Wout + TC - 1) / TC;

@@ -10,7 +10,9 @@
 //     (k=3: 144, k=5: 200, k=7: 196) that persist across the workgroup's pixel tiles, so a tile costs no
 //     epilogue; gY fragments come straight from L2 (each element is used by one wave only);
 //   * workgroups stride over pixel tiles; one partial slab per workgroup row, reduced without atomics by
-//     cconv_wgrad_reduce_kernel (conv_direct.hip), which also writes the reference's parameter layout.
+//     wgrad_reduce.hip, which also writes the reference's parameter layout.
+// Host side: dcs_conv_wgrad_mfma_plan is the ONE place that decides the route (folded or plain), the tile, the slab
+// count and the workspace layout (conv::WgradLayout); conv_api.hip's query and launch both read it.
 #include "conv_common.h"
 #include "wgrad_reduce.h"
 #include <cstdlib>
@@ -1093,12 +1095,13 @@ long planes_bytes_for(const conv::Args& c, int ncls, int TH, int TW) {
     return (long)ncls * tiles * ((TH * TW) >> 5) * 3 * (2 * c.Cout / 16) * 64 * (long)sizeof(uint4);
 }
 
-// c: class-space geometry; f: classes; Hy x Wy: full g_Y extent; planes: room for planes_bytes_for(...) bytes, or nullptr
+// c: class-space geometry; f: classes; Hy x Wy: full g_Y extent; planes: the plan's planes region (planes_bytes_for(...) > 0
+// bytes), or nullptr
 int launch_classes(const conv::Args& c, const Fold& f, int Hy, int Wy, const act_t* gy, float2* slab_w, float* slab_b,
                    int n_slabs, int TH, int TW, hipStream_t stream, void* planes = nullptr) {
     WArgs w;
     w.c = c;
-    w.gy_planes = (planes && planes_bytes_for(c, f.ncls, TH, TW) > 0) ? (const uint4*)planes : nullptr;
+    w.gy_planes = (const uint4*)planes;
 #ifdef DCS_WGRAD_DIAG
     w.dbg = g_wdbg;
 #else
@@ -1129,36 +1132,9 @@ bool dcs_conv_wgrad_mfma_ok(int Cin, int Cout, int kh, int kw, int C1) {
     return (Cin % 8) == 0 && (Cout % 8) == 0 && kh == kw && (kh == 1 || kh == 3 || kh == 5 || kh == 7) && !(C1 & 1);
 }
 
-// number of partial slabs and the tile shape for a forward geometry (a.Hout / a.Wout set)
-int dcs_conv_wgrad_mfma_slabs(const conv::Args& a, int* TH, int* TW) {
-    tile_shape_for(a, a.Hout, a.Wout, TH, TW);
-    return slabs_for(a, 1, *TH, *TW);
-}
-
-// slab_w: float2[n_slabs][taps][Cin][Cout]; slab_b: float[n_slabs][2*Cout]
-int dcs_conv_wgrad_mfma_launch(conv::Args& a, const act_t* gy, float2* slab_w, float* slab_b, int n_slabs,
-                               hipStream_t stream, void* planes) {
-    int TH, TW;
-    tile_shape_for(a, a.Hout, a.Wout, &TH, &TW);
-    Fold f{};
-    f.ncls = 1; f.kh = a.kh; f.kw = a.kw; f.os_f = 1; f.os_t = 1;
-    f.pad_f[0] = a.pad_f; f.pad_t[0] = a.pad_t;
-    return launch_classes(a, f, a.Hout, a.Wout, gy, slab_w, slab_b, n_slabs, TH, TW, stream, planes);
-}
-
-// bytes of the pre-split g_Y the plain (unfolded) launch of geometry `a` can use (0: none) — behind the slabs in the workspace
-long dcs_conv_wgrad_mfma_planes_bytes(const conv::Args& a) {
-    int TH, TW;
-    tile_shape_for(a, a.Hout, a.Wout, &TH, &TW);
-    return planes_bytes_for(a, 1, TH, TW);
-}
-
-// upsample-folded path: forward geometry `a` (a.Hout / a.Wout set) of a 3x3 stride-1 pad-1 conv over an upsampled input
-bool dcs_conv_wgrad_fold_ok(const conv::Args& a) {
-    const int Cin = a.C1 + a.C2;
-    if (!(dcs_conv_wgrad_mfma_ok(Cin, a.Cout, a.kh, a.kw, a.C1) &&
-          conv::fold_ok(Cin, a.Cout, a.kh, a.kw, a.sf, a.st, a.pad_f, a.pad_t, a.up_f, a.up_t)))
-        return false;
+// upsample-folded route: forward geometry `a` (a.Hout / a.Wout set) of a 3x3 stride-1 pad-1 conv over an upsampled input
+static bool fold_route(const conv::Args& a) {
+    if (!conv::fold_ok(a.C1 + a.C2, a.Cout, a.kh, a.kw, a.sf, a.st, a.pad_f, a.pad_t, a.up_f, a.up_t)) return false;
     // 128-pixel tiles x taps actually issued: a class of a very small source map (dec0: 2 x 32) can fill its tiles
     // worse than the plain form does
     const Fold f = fold_of(a);
@@ -1170,37 +1146,46 @@ bool dcs_conv_wgrad_fold_ok(const conv::Args& a) {
     return folded < plain;
 }
 
-long dcs_conv_wgrad_fold_workspace_bytes(const conv::Args& a) {
-    const Fold f = fold_of(a);
-    const conv::Args c = class_args(a, f);
-    int TH, TW;
-    tile_shape_for(c, c.Hout, c.Wout, &TH, &TW);
-    const long ns = slabs_for(c, f.ncls, TH, TW);
-    const long slabs = ns * f.ncls * ((long)f.kh * f.kw * (a.C1 + a.C2) * a.Cout + a.Cout) * (long)sizeof(float2);
-    return ((slabs + 255) & ~255L) + planes_bytes_for(c, f.ncls, TH, TW);       // (+ the pre-split g_Y behind the slabs)
+conv::WgradLayout dcs_conv_wgrad_mfma_plan(const conv::Args& a) {
+    conv::WgradLayout p{};
+    p.fold = fold_route(a);
+    conv::Args c = a;                       // the geometry the kernel tiles: the conv itself, or one parity class of it
+    p.ncls = 1;
+    if (p.fold) {                           // (fold_of only behind conv::fold_ok: it holds four classes, upsample factors 1 or 2)
+        const Fold f = fold_of(a);
+        c = class_args(a, f);
+        p.ncls = f.ncls;
+    }
+    tile_shape_for(c, c.Hout, c.Wout, &p.TH, &p.TW);
+    p.n_slabs = slabs_for(c, p.ncls, p.TH, p.TW);
+    p.wsz = (long)c.kh * c.kw * (a.C1 + a.C2) * a.Cout;
+    p.slab_bytes = (long)p.n_slabs * p.ncls * (p.wsz + a.Cout) * (long)sizeof(float2);
+    p.planes_off = conv::align256(p.slab_bytes);
+    p.planes_bytes = planes_bytes_for(c, p.ncls, p.TH, p.TW);
+    p.bytes = p.planes_bytes > 0 ? p.planes_off + p.planes_bytes : p.slab_bytes;
+    return p;
 }
 
-int dcs_conv_wgrad_fold_run(const conv::Args& a, const act_t* gy, void* workspace, long workspace_bytes, float* gw_r,
-                            float* gw_i, float* gb_r, float* gb_i, int transposed, hipStream_t stream) {
-    if (!dcs_conv_wgrad_fold_ok(a)) return DCS_ERR_BADARG;
+// slab_w: float2[n_slabs][taps][Cin][Cout]; slab_b: float[n_slabs][2*Cout]
+int dcs_conv_wgrad_mfma_launch(conv::Args& a, const conv::WgradLayout& p, const act_t* gy, float2* slab_w, float* slab_b,
+                               void* planes, hipStream_t stream) {
+    Fold f{};
+    f.ncls = 1; f.kh = a.kh; f.kw = a.kw; f.os_f = 1; f.os_t = 1;
+    f.pad_f[0] = a.pad_f; f.pad_t[0] = a.pad_t;
+    return launch_classes(a, f, a.Hout, a.Wout, gy, slab_w, slab_b, p.n_slabs, p.TH, p.TW, stream, planes);
+}
+
+int dcs_conv_wgrad_fold_run(const conv::Args& a, const conv::WgradLayout& p, const act_t* gy, float2* slab_w, float2* slab_b,
+                            void* planes, float* gw_r, float* gw_i, float* gb_r, float* gb_i, int transposed,
+                            hipStream_t stream) {
+    if (!p.fold) return DCS_ERR_BADARG;
     const Fold f = fold_of(a);
     const conv::Args c = class_args(a, f);
-    int TH, TW;
-    tile_shape_for(c, c.Hout, c.Wout, &TH, &TW);
-    const int ns = slabs_for(c, f.ncls, TH, TW);
-    const int Cin = a.C1 + a.C2;
-    const long wsz_c = (long)f.kh * f.kw * Cin * a.Cout;
-    if (workspace_bytes < (long)ns * f.ncls * (wsz_c + a.Cout) * (long)sizeof(float2)) return DCS_ERR_WORKSPACE;
-    float2* slab_w = (float2*)workspace;
-    float2* slab_b = slab_w + (long)ns * f.ncls * wsz_c;
-    const long slabs = (long)ns * f.ncls * (wsz_c + a.Cout) * (long)sizeof(float2), pb = planes_bytes_for(c, f.ncls, TH, TW);
-    void* planes = (pb > 0 && workspace_bytes >= ((slabs + 255) & ~255L) + pb) ? (char*)workspace + ((slabs + 255) & ~255L) : nullptr;
-    const int rc = launch_classes(c, f, a.Hout, a.Wout, gy, slab_w, (float*)slab_b, ns, TH, TW, stream, planes);
+    const int rc = launch_classes(c, f, a.Hout, a.Wout, gy, slab_w, (float*)slab_b, p.n_slabs, p.TH, p.TW, stream, planes);
     if (rc != DCS_OK) return rc;
     wreduce::Job j{};                                     // class gradients -> 3x3 parameter (wgrad_reduce.hip)
     j.slab_w = slab_w; j.slab_b = slab_b; j.gw_r = gw_r; j.gw_i = gw_i; j.gb_r = gb_r; j.gb_i = gb_i;
-    j.n_slabs = ns; j.Cout = a.Cout; j.Cin = Cin; j.kh = 3; j.kw = 3; j.transposed = transposed;
+    j.n_slabs = p.n_slabs; j.Cout = a.Cout; j.Cin = a.C1 + a.C2; j.kh = 3; j.kw = 3; j.transposed = transposed;
     j.up_f = a.up_f; j.up_t = a.up_t;
     return wreduce::emit(j, stream);
-    return DCS_OK;
 }

@@ -255,7 +255,7 @@ std::mutex g_small_mutex;
 
 }  // namespace
 
-// forward geometry `a` (fwd_args + conv_geometry of conv_direct.hip: 16x16 tiles)
+// forward geometry `a` (conv_api.hip: fwd_args + dcs_conv_geometry of conv_direct.hip: 16x16 tiles)
 bool dcs_conv_wgrad_small_ok(const conv::Args& a) {
     if (a.kh != KS || a.kw != KS || a.up_f != 1 || a.up_t != 1 || a.C2 != 0 || a.sf != a.st) return false;
     if (a.C1 == 2 && a.Cout == 1 && a.sf == 1) return true;

@@ -57,6 +57,7 @@ SIGNATURES = {
     'dcs_cconv2d_bwd_data': (_I, [_P] * 5 + [_L] + [_I] * 14 + [_P]),
     'dcs_upsample_cat_bwd': (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     'dcs_cconv2d_bwd_weight_workspace_bytes': (_L, [_I] * 14),
+    'dcs_cconv2d_bwd_weight_plan': (_I, [_I] * 14 + [_P]),
     'dcs_cconv2d_bwd_weight': (_I, [_P] * 8 + [_L] + [_I] * 15 + [_P]),
     'dcs_cbn_workspace_bytes': (_L, [_L, _I]),
     'dcs_cbn_fwd': (_I, [_P] * 9 + [_L, _L, _I, _F, _F, _I, _I, _F, _U64, _P, _P]),
@@ -185,6 +186,7 @@ class DcsHipError(RuntimeError):
 
 # bf16-activation forms (include/dcsnet_hip.h, last section): the same argument lists as the fp32 entry points they mirror
 for _n in ('dcs_cconv2d_fwd', 'dcs_cconv2d_fwd_affine', 'dcs_cconv2d_fwd_stats', 'dcs_cconv2d_bwd_data', 'dcs_cconv2d_bwd_weight',
+           'dcs_cconv2d_bwd_weight_workspace_bytes', 'dcs_cconv2d_bwd_weight_plan',
            'dcs_cconv_up2_single_fwd', 'dcs_cconv_up2_single_bwd_data', 'dcs_cconv_up2_single_bwd_weight', 'dcs_tapsum_bwd', 'dcs_cbn_fwd', 'dcs_cbn_fwd_slabs', 'dcs_cbn_fwd_slabs_pool', 'dcs_cbn_bwd', 'dcs_cbn_bwd_add',
            'dcs_channel_attention_fwd', 'dcs_spatial_pool_fwd', 'dcs_attention_apply_fwd', 'dcs_attention_fwd_batched',
            'dcs_attention_bwd_sa', 'dcs_attention_bwd_x', 'dcs_attention_bwd_batched'):

@@ -214,14 +214,9 @@ def tap_rows_scatter(gt_r, gt_i, w_shape, outs=None):
     return g_r, g_i
 
 
-def cconv2d(x1, x2, wp, bias, ksize, stride=(1, 1), pad=(0, 0), up=(1, 1), act=ACT_NONE, coef=None):
-    """Complex correlation over the virtual input upsample(cat(x1, x2)); see dcs_cconv2d_fwd.  coef [Cout, 6]: an eval-mode
-    CBN's coefficients folded in between bias and activation (dcs_cconv2d_fwd_affine)."""
-    _chk(x1, 'x1', 5, act=True)
-    _chk(x2, 'x2', 5, act=True)
-    _chk(wp, 'wp', 4)
-    _chk(bias, 'bias', 2)
-    B, Hin, Win, C1, _ = x1.shape
+def _conv_fwd_extent(x1, x2, wp, ksize, stride, pad, up):
+    """Shape checks of a forward conv call (cconv2d, cconv2d_stats) and its output extent -> (Hout, Wout)."""
+    _, Hin, Win, C1, _ = x1.shape
     C2 = 0
     if x2 is not None:
         if x2.shape[:3] != x1.shape[:3]:
@@ -230,9 +225,34 @@ def cconv2d(x1, x2, wp, bias, ksize, stride=(1, 1), pad=(0, 0), up=(1, 1), act=A
     kh, kw = ksize
     if wp.shape[0] != kh * kw or wp.shape[1] != C1 + C2:
         raise _lib.DcsHipError(f'cconv2d: packed weight {tuple(wp.shape)} does not match k={ksize}, Cin={C1 + C2}')
+    return (Hin * up[0] + 2 * pad[0] - kh) // stride[0] + 1, (Win * up[1] + 2 * pad[1] - kw) // stride[1] + 1
+
+
+def _conv_fwd_timer(x1, C2, Hout, Wout, Cout, ksize, stride, pad, up):
+    """bench.py's live roofline probe for a forward conv launch: 8 real flops per complex MAC.  Strided
+    forward convs are exactly the encoder's ComplexConv2d stack: tagged for bench.py's encoder roofline."""
+    if CONV_TIMER is None:
+        return None
+    B, Hin, Win, C1, _ = x1.shape
+    kh, kw = ksize
+    return CONV_TIMER.begin(8.0 * B * Hout * Wout * Cout * (C1 + C2) * kh * kw, 'enc_fwd' if max(stride) > 1 else None,
+                            executed=_fold_fraction(C1, C1 + C2, Cout, ksize, stride, pad, up),
+                            emulated=_emulated(C1 + C2, Cout, kh * kw if tuple(up) == (1, 1) else 0) and (C1 % 2 == 0 or C1 + C2 == 1),
+                            nbytes=_conv_bytes(x1, B * Hin * Win * (C1 + C2), B * Hout * Wout * Cout, kh * kw * (C1 + C2) * Cout))
+
+
+def cconv2d(x1, x2, wp, bias, ksize, stride=(1, 1), pad=(0, 0), up=(1, 1), act=ACT_NONE, coef=None):
+    """Complex correlation over the virtual input upsample(cat(x1, x2)); see dcs_cconv2d_fwd.  coef [Cout, 6]: an eval-mode
+    CBN's coefficients folded in between bias and activation (dcs_cconv2d_fwd_affine)."""
+    _chk(x1, 'x1', 5, act=True)
+    _chk(x2, 'x2', 5, act=True)
+    _chk(wp, 'wp', 4)
+    _chk(bias, 'bias', 2)
+    B, Hin, Win, C1, _ = x1.shape
+    C2 = 0 if x2 is None else x2.shape[3]
+    kh, kw = ksize
     Cout = wp.shape[2]
-    Hout = (Hin * up[0] + 2 * pad[0] - kh) // stride[0] + 1
-    Wout = (Win * up[1] + 2 * pad[1] - kw) // stride[1] + 1
+    Hout, Wout = _conv_fwd_extent(x1, x2, wp, ksize, stride, pad, up)
     y = torch.empty((B, Hout, Wout, Cout, 2), dtype=x1.dtype, device=x1.device)
     lib = _lib.load()
     # split-K scratch for layers with too few output tiles to fill the chip (0 bytes for most geometries)
@@ -240,13 +260,7 @@ def cconv2d(x1, x2, wp, bias, ksize, stride=(1, 1), pad=(0, 0), up=(1, 1), act=A
                                                  pad[0], pad[1])
     ws = _workspace(nbytes, x1.device) if nbytes > 0 else None
     nbytes = max(nbytes, 0)
-    # bench.py's live roofline probe: 8 real flops per complex MAC
-    # (strided forward convs are exactly the encoder's ComplexConv2d stack: tagged for bench.py's encoder roofline)
-    ev = (CONV_TIMER.begin(8.0 * B * Hout * Wout * Cout * (C1 + C2) * kh * kw, 'enc_fwd' if max(stride) > 1 else None,
-                           executed=_fold_fraction(C1, C1 + C2, Cout, ksize, stride, pad, up),
-                           emulated=_emulated(C1 + C2, Cout, kh * kw if tuple(up) == (1, 1) else 0) and (C1 % 2 == 0 or C1 + C2 == 1),
-                           nbytes=_conv_bytes(x1, B * Hin * Win * (C1 + C2), B * Hout * Wout * Cout, kh * kw * (C1 + C2) * Cout))
-          if CONV_TIMER is not None else None)
+    ev = _conv_fwd_timer(x1, C2, Hout, Wout, Cout, ksize, stride, pad, up)
     if coef is not None:
         _chk(coef, 'coef', 2)
         if tuple(coef.shape) != (Cout, 6):
@@ -277,21 +291,12 @@ def cconv2d_stats(x1, x2, wp, bias, ksize, stride=(1, 1), pad=(0, 0), up=(1, 1))
     rows = lib.dcs_cconv2d_fwd_stats_rows(*geo) if STATS_EPILOGUE else 0
     if rows < 1:
         return cconv2d(x1, x2, wp, bias, ksize, stride, pad, up, ACT_NONE), None
-    if x2 is not None and x2.shape[:3] != x1.shape[:3]:
-        raise _lib.DcsHipError(f'cconv2d: x1 {tuple(x1.shape)} and x2 {tuple(x2.shape)} differ in B/H/W')
-    if wp.shape[0] != kh * kw or wp.shape[1] != C1 + C2:
-        raise _lib.DcsHipError(f'cconv2d: packed weight {tuple(wp.shape)} does not match k={ksize}, Cin={C1 + C2}')
-    Hout = (Hin * up[0] + 2 * pad[0] - kh) // stride[0] + 1
-    Wout = (Win * up[1] + 2 * pad[1] - kw) // stride[1] + 1
+    Hout, Wout = _conv_fwd_extent(x1, x2, wp, ksize, stride, pad, up)
     y = torch.empty((B, Hout, Wout, Cout, 2), dtype=x1.dtype, device=x1.device)
     part = torch.empty((Cout, 5, rows), dtype=torch.float32, device=x1.device)
     nbytes = max(lib.dcs_cconv2d_fwd_workspace_bytes(*geo), 0)
     ws = _workspace(nbytes, x1.device) if nbytes > 0 else None
-    ev = (CONV_TIMER.begin(8.0 * B * Hout * Wout * Cout * (C1 + C2) * kh * kw, 'enc_fwd' if max(stride) > 1 else None,
-                           executed=_fold_fraction(C1, C1 + C2, Cout, ksize, stride, pad, up),
-                           emulated=_emulated(C1 + C2, Cout, kh * kw if tuple(up) == (1, 1) else 0) and (C1 % 2 == 0 or C1 + C2 == 1),
-                           nbytes=_conv_bytes(x1, B * Hin * Win * (C1 + C2), B * Hout * Wout * Cout, kh * kw * (C1 + C2) * Cout))
-          if CONV_TIMER is not None else None)
+    ev = _conv_fwd_timer(x1, C2, Hout, Wout, Cout, ksize, stride, pad, up)
     used = ctypes.c_int(0)
     check(_sym('dcs_cconv2d_fwd_stats', x1, x2)(ptr(x1), ptr(x2), ptr(wp), ptr(bias), ptr(y), ptr(part), rows, ctypes.byref(used), ptr(ws),
                                     nbytes, *geo, cur_stream()), 'dcs_cconv2d_fwd_stats')
@@ -417,7 +422,7 @@ def cconv2d_bwd_weight(x1, x2, gy, w_shape, has_bias, ksize, stride, pad, up=(1,
         _chk(t, n)
     lib = _lib.load()
     geo = (B, Hin, Win, C1, C2, up[0], up[1], Cout, ksize[0], ksize[1], stride[0], stride[1], pad[0], pad[1])
-    nbytes = lib.dcs_cconv2d_bwd_weight_workspace_bytes(*geo)
+    nbytes = _sym('dcs_cconv2d_bwd_weight_workspace_bytes', x1, x2, gy)(*geo)      # (the build's own: its launch's arithmetic)
     if nbytes < 0:
         raise _lib.DcsHipError(f'cconv2d_bwd_weight: unsupported geometry {geo}')
     # Inside a deferred-reduce scope (wgrad_defer_begin) the slab reduce of this call is postponed to the flush when ALL

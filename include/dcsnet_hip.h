@@ -106,6 +106,10 @@ int dcs_pack_conv_weight(const float* w_r, const float* w_i, const float* b_r, c
  * layers at small batch have too few output tiles to fill 256 CUs; with the scratch their input-channel range is
  * sliced over extra workgroups and a reduce pass adds the slices (+ bias, activation) in a fixed order.  NULL or too
  * small: the layer simply runs unsliced.
+ * This query, dcs_cconv2d_fwd_stats_rows and dcs_cconv2d_bwd_data_workspace_bytes exist in the fp32 form only and also size the
+ * _h launches: the bf16 build plans with the same host arithmetic under the same conv precision, and over every geometry of
+ * the test tables and every conv layer of both networks at [32,256,256] and [16,256,2000] its answers never differ from
+ * these (profiles/conv_api_refactor.txt, section 3; the opt-in DCS_CONV_RING=1 kernel, whose plan depends on the build, aside).
  */
 long dcs_cconv2d_fwd_workspace_bytes(int B, int Hin, int Win, int C1, int C2, int up_f, int up_t,
                                      int Cout, int kh, int kw, int sf, int st, int pad_f, int pad_t);
@@ -123,7 +127,8 @@ int dcs_cconv2d_fwd(const float* x1, const float* x2, const float* wp, const flo
  *   stat_rows   capacity of `stat` in rows, >= dcs_cconv2d_fwd_stats_rows(geometry) (0 there: this geometry has no
  *               statistics epilogue — use dcs_cconv2d_fwd + dcs_cbn_fwd)
  *   rows_used   HOST int, out: rows written (depends on whether the split-K scratch was handed over)
- * Consumer: dcs_cbn_fwd_slabs(part = stat, rows = *rows_used, stride = stat_rows, pivot = bias). */
+ * Consumer: dcs_cbn_fwd_slabs(part = stat, rows = *rows_used, stride = stat_rows, pivot = bias).
+ * (dcs_cconv2d_fwd_stats_rows also answers for dcs_cconv2d_fwd_stats_h: see dcs_cconv2d_fwd_workspace_bytes.) */
 int dcs_cconv2d_fwd_stats_rows(int B, int Hin, int Win, int C1, int C2, int up_f, int up_t,
                                int Cout, int kh, int kw, int sf, int st, int pad_f, int pad_t);
 int dcs_cconv2d_fwd_stats(const float* x1, const float* x2, const float* wp, const float* bias, float* y,
@@ -204,14 +209,25 @@ int dcs_rbn_bwd(const float* x, const float* g_out, float* g_x, const float* sta
  *     block-summed over the upsample factors and split at channel C1.  workspace: the first part (required when
  *     the virtual-input gradient has to exist: cat or upsample on a non-folded geometry) holds g_Xv, the rest is the
  *     optional split-K scratch of the deep few-pixel layers (as in dcs_cconv2d_fwd);
- *     dcs_cconv2d_bwd_data_workspace_bytes returns the sum (0 for most geometries).
+ *     dcs_cconv2d_bwd_data_workspace_bytes returns the sum (0 for most geometries; also for the _h launch: see
+ *     dcs_cconv2d_fwd_workspace_bytes).
  * dcs_upsample_cat_bwd:  the stand-alone block sum / channel split of a virtual-input gradient.
  * dcs_cconv2d_bwd_weight: gradients of the reference's parameters, in THEIR layout:
  *     gw_r, gw_i: float[Cout][Cin][kh][kw] (transposed=0) or float[Cin][Cout][kh][kw] (transposed=1)
  *     gb_r, gb_i: float[Cout] (NULL for bias-free layers).  x1/x2/geometry as in the forward call.
- *     workspace >= dcs_cconv2d_bwd_weight_workspace_bytes(...): the partial slabs (no atomics) and, behind them, the cotangent
- *     split once into its three bf16 planes for layers of >= 64 input channels in the emulated-fp32 mode (a workspace that
- *     holds the slabs only is accepted: the kernels then split in place).  The call reads x1 / x2 / gy and the workspace
+ *     workspace >= dcs_cconv2d_bwd_weight_workspace_bytes(...), laid out (one description, read by the query, by
+ *     dcs_cconv2d_bwd_weight_plan and by the launch) as
+ *         [ weight slabs float2[slabs][classes][taps x Cin x Cout] | bias slabs float2[slabs][classes][Cout] |
+ *           pad to a multiple of 256 bytes | planes ]
+ *     slabs: the kernels' partial sums (no atomics), reduced in a fixed order; classes: 1, or the parity classes of a 3x3
+ *     conv behind a nearest upsample (their taps are the folded kernel's).  planes: the cotangent split once into its three
+ *     bf16 planes, for layers of >= 64 input channels in the emulated-fp32 mode; absent (0 bytes, and no padding) everywhere
+ *     else and under bf16 storage.  A workspace smaller than the slabs is DCS_ERR_WORKSPACE before any launch; one that
+ *     holds the slabs but not the planes is accepted: the kernels then split in place.  The query is the launch's own
+ *     arithmetic, so the _h launch is sized by the _h query (slab counts follow the build's own kernels).
+ *     dcs_cconv2d_bwd_weight_plan: out[5] = {route (0 MFMA folded, 1 MFMA, 2 enc0, 3 small 7x7, 4 direct), slabs, slab bytes,
+ *     planes bytes, total bytes = the query's answer}; host arithmetic only.  Both return -1 for a geometry the launch rejects.
+ *     The call reads x1 / x2 / gy and the workspace
  *     until its stream has run it — on a side stream (as dcsnet/dp.py issues it) keep them alive until that stream is joined. */
 long dcs_packed_weight_bwd_floats(int Cout, int Cin, int kh, int kw, int sf, int st, int pad_f, int pad_t,
                                   int up_f, int up_t);
@@ -227,6 +243,8 @@ int  dcs_upsample_cat_bwd(const float* gxv, float* gx1, float* gx2, int B, int H
                           int up_f, int up_t, dcs_stream_t stream);
 long dcs_cconv2d_bwd_weight_workspace_bytes(int B, int Hin, int Win, int C1, int C2, int up_f, int up_t,
                                             int Cout, int kh, int kw, int sf, int st, int pad_f, int pad_t);
+int  dcs_cconv2d_bwd_weight_plan(int B, int Hin, int Win, int C1, int C2, int up_f, int up_t,
+                                 int Cout, int kh, int kw, int sf, int st, int pad_f, int pad_t, long* out);
 int  dcs_cconv2d_bwd_weight(const float* x1, const float* x2, const float* gy,
                             float* gw_r, float* gw_i, float* gb_r, float* gb_i,
                             void* workspace, long workspace_bytes,
@@ -990,7 +1008,8 @@ int dcs_segments_stitch_f32(const float* seg, long seg_rows, const int* seg_firs
  * operand (packed weights, biases, CBN parameters / statistics / coefficients, the per-sample and per-pixel attention maps
  * ca / sa / pooled / hidden / sp / g_pre / g_sp, split-K and weight-gradient slabs, parameter gradients) stays fp32.
  * Kernels read bf16, compute in fp32 (MFMA: bf16 operands, fp32 accumulate) and round once on store.  Requires
- * dcs_set_conv_precision(1) (bf16 weight panels).  Workspace sizes are those of the fp32 queries.
+ * dcs_set_conv_precision(1) (bf16 weight panels).  Workspace sizes are those of the fp32 queries, except the weight
+ * gradient's, which has its own (dcs_cconv2d_bwd_weight_workspace_bytes_h / _plan_h).
  * In dcs_attention_item the fields x, y, g_out, g_x are bf16 tensors for the _h batched calls.  dcs_cconv_up2_single_fwd_h
  * reads bf16 sources and writes the network's fp32 mask; dcs_tapsum_bwd_h reads the fp32 mask cotangent and writes bf16. */
 typedef unsigned short dcs_bf16_t;
@@ -1010,6 +1029,10 @@ int dcs_cconv2d_bwd_data_h(const dcs_bf16_t* gy, const float* wp_bwd, dcs_bf16_t
                            void* workspace, long workspace_bytes,
                            int B, int Hin, int Win, int C1, int C2, int up_f, int up_t,
                            int Cout, int kh, int kw, int sf, int st, int pad_f, int pad_t, dcs_stream_t stream);
+long dcs_cconv2d_bwd_weight_workspace_bytes_h(int B, int Hin, int Win, int C1, int C2, int up_f, int up_t,
+                                              int Cout, int kh, int kw, int sf, int st, int pad_f, int pad_t);
+int dcs_cconv2d_bwd_weight_plan_h(int B, int Hin, int Win, int C1, int C2, int up_f, int up_t,
+                                  int Cout, int kh, int kw, int sf, int st, int pad_f, int pad_t, long* out);
 int dcs_cconv2d_bwd_weight_h(const dcs_bf16_t* x1, const dcs_bf16_t* x2, const dcs_bf16_t* gy,
                              float* gw_r, float* gw_i, float* gb_r, float* gb_i, void* workspace, long workspace_bytes,
                              int B, int Hin, int Win, int C1, int C2, int up_f, int up_t,
