@@ -11,6 +11,9 @@ it (mean val_loss in dcs / drs mode, the epoch's mean speech_loss in dc / dr mod
 writer, best.ckpt when the monitored value improved; one JSON line appended to metrics.jsonl.  After the last epoch
 on_train_end() and a synchronous final.ckpt: it holds the SWA weights and is what the enhancement tools should load.
 
+validation='device' replaces the validation pass by validation.DeviceValidator: the same crops, losses, STOI and the epoch's
+means on the device, one host read per epoch; 'host', the default, is the pass described above.
+
 Checkpoints are taken at epoch boundaries; resume='auto' continues from out_dir/last.ckpt when it exists (a path: from that
 file).  In a multi-rank run every rank loads and rank 0 writes (untested: one GPU per machine).  What a resumed run reproduces
 is stated in DESIGN.md §6f.
@@ -61,11 +64,19 @@ def validate(net, val_store, batch_size, seed, epoch):
     return {k: float(torch.stack([torch.as_tensor(o[k]).float().cpu() for o in outs]).mean()) for k in keys}
 
 
+VALIDATION = ('host', 'device')
+
+
 def fit(net, train_store, val_store, out_dir, max_epochs, batch_size, use_graph=True, resume=None, seed=_config.seed,
-        stop_after_epoch=None, log=print):
+        stop_after_epoch=None, log=print, validation='host'):
     """Train `net` for max_epochs (plus the statistics epoch where SWA needs one); returns a summary dict: epoch (the last one
     run), global_step, lr, scheduler ('plateau' | 'swalr' | None), n_averaged, best, finished, and the live `step` / `swa`.
-    stop_after_epoch: return after that epoch's checkpoint — the process can stop at any epoch boundary."""
+    stop_after_epoch: return after that epoch's checkpoint — the process can stop at any epoch boundary.
+    validation: 'host' — validate() below, the reference's procedure — or 'device': one validation.DeviceValidator for the run (the
+    same crops; losses, STOI and the epoch's means on the device, one host read per epoch, val_pesq NaN); the metrics line then
+    also carries val_skipped."""
+    if validation not in VALIDATION:
+        raise ValueError(f'fit: validation={validation!r}: expected one of {VALIDATION}')
     from ._pl_compat import seed_everything
     from .checkpoint import CheckpointWriter, load_checkpoint, save_checkpoint
     from .dp import TrainStep, plateau_scheduler
@@ -95,6 +106,10 @@ def fit(net, train_store, val_store, out_dir, max_epochs, batch_size, use_graph=
         os.remove(metrics_path)
     writer = CheckpointWriter(step, swa) if rank == 0 and step.bucket.flat.is_cuda else None
     validates = _mode() in ('dcs', 'drs')
+    validator = None
+    if validation == 'device' and val_store is not None:
+        from .validation import DeviceValidator
+        validator = DeviceValidator(net, val_store, batch_size, seed=seed)
     epoch = start - 1
     try:
         for epoch in range(start, swa.epochs):
@@ -118,7 +133,10 @@ def fit(net, train_store, val_store, out_dir, max_epochs, batch_size, use_graph=
                 if writer is not None:
                     writer.poll()
             train_loss = _mean(losses)
-            val = validate(net, val_store, batch_size, seed, epoch) if val_store is not None else {}
+            if validator is not None:
+                val = dict(validator.run(epoch), val_skipped=validator.counts['skipped'])
+            else:
+                val = validate(net, val_store, batch_size, seed, epoch) if val_store is not None else {}
             monitored = val.get('val_loss', train_loss) if validates else train_loss
             swa.on_train_epoch_end(epoch, monitored=monitored)
             improved = monitored == monitored and (best is None or monitored < best)

@@ -1782,6 +1782,33 @@ def swa_average(avg, p, n_averaged):
     return avg
 
 
+# ---- the validation epoch's books (csrc/validation.hip, dcsnet/validation.py) -------------------------------------------
+
+VAL_STATE, VAL_MAX_SCORES = 16, 4                                   # DCS_VAL_* (include/dcsnet_hip.h)
+VAL_LOSS_SUM, VAL_SCORE_SUM, VAL_KEPT, VAL_SKIPPED, VAL_SCORE_NAN = 0, 3, 7, 8, 9
+
+
+def val_accumulate(losses, scores, state):
+    """Fold one validation batch into `state` in place (dcs_val_accumulate_f32: the rule is in the header).  losses: float32 [3]
+    (noise, speech, total) or [1] (speech); scores: float32 [n_scores, B] (or [B]: one row), or None; state: float64
+    [VAL_STATE] on the same device.  One launch, no read-back."""
+    _chk(losses, 'losses', 1)
+    _chk(scores, 'scores')
+    if scores is not None and scores.dim() == 1:
+        scores = scores.unsqueeze(0)
+    if scores is not None and scores.dim() != 2:
+        raise _lib.DcsHipError(f'val_accumulate: scores must be [n_scores, B], got {tuple(scores.shape)}')
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and
+            state.numel() == VAL_STATE and state.device == losses.device):
+        raise _lib.DcsHipError(f'val_accumulate: state must be a contiguous float64 [{VAL_STATE}] tensor on {losses.device}')
+    if scores is not None and scores.device != losses.device:
+        raise _lib.DcsHipError(f'val_accumulate: scores on {scores.device}, losses on {losses.device}')
+    n_scores, B = (0, 1) if scores is None else (int(scores.shape[0]), int(scores.shape[1]))
+    check(_lib.load().dcs_val_accumulate_f32(ptr(losses), losses.numel(), ptr(scores) if n_scores else None, n_scores, B,
+                                             ptr(state), cur_stream()), 'dcs_val_accumulate_f32')
+    return state
+
+
 # ---- checkpoint snapshot (csrc/snapshot.hip, dcsnet/checkpoint.py) ------------------------------------------------------
 
 SNAPSHOT_BLOCK_WORDS = 1024          # DCS_SNAPSHOT_BLOCK_WORDS (include/dcsnet_hip.h)

@@ -952,6 +952,33 @@ int dcs_frame_measures_ragged_f32(const float* clean, const float* est, const lo
                                   void* workspace, long workspace_bytes, dcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The books of a validation epoch on the device (dcsnet/validation.py), validation.hip: one launch per batch folds the batch
+ * into `state`, so an epoch ends with one host read.  losses: device float[n_loss], n_loss = 3 (noise, speech, total) or 1
+ * (speech); the MONITORED loss is losses[n_loss - 1].  scores: device float[n_scores][B], 0 <= n_scores <= DCS_VAL_MAX_SCORES,
+ * one row per per-utterance score (STOI, then ESTOI).  state: device double[DCS_VAL_STATE], zeroed by the caller before an epoch:
+ *   [DCS_VAL_LOSS_SUM + k]   sum over the kept batches of losses[k], k < n_loss
+ *   [DCS_VAL_SCORE_SUM + r]  sum over the kept batches of row r's batch mean, r < n_scores
+ *   [DCS_VAL_KEPT]           batches kept            [DCS_VAL_SKIPPED]  batches skipped
+ *   [DCS_VAL_SCORE_NAN + r]  NaN utterances of row r in the kept batches
+ * (counts are integers held in doubles: exact).  The rule per launch is the reference's: a NaN monitored loss skips the batch —
+ * skipped += 1 and nothing else changes (validation_step returns None, c_network.py:298-300); only NaN skips, +-Inf is kept and
+ * propagates.  A kept batch adds 1 to kept, every loss component to its sum, and per score row the batch mean = (sum of the
+ * non-NaN entries) / max(their count, 1) — an all-NaN row adds 0.0 (calc_metric, network_functions.py:152-166) — and the row's
+ * NaN count.  The epoch mean is sum / kept, a mean of batch means (_epoch_end), divided on the host.
+ * One workgroup of 256 threads, grid-stride over B, fp64 sums in a fixed order, no atomics (launches on one stream are ordered;
+ * thread 0 updates state with plain stores): bit-reproducible, no sync, no read-back, capturable.  Null losses / state, n_loss
+ * not 1 or 3, n_scores outside [0, DCS_VAL_MAX_SCORES], n_scores > 0 with null scores, B < 1: DCS_ERR_BADARG before any launch. */
+#define DCS_VAL_STATE      16
+#define DCS_VAL_MAX_SCORES 4
+#define DCS_VAL_LOSS_SUM   0
+#define DCS_VAL_SCORE_SUM  3
+#define DCS_VAL_KEPT       7
+#define DCS_VAL_SKIPPED    8
+#define DCS_VAL_SCORE_NAN  9
+int dcs_val_accumulate_f32(const float* losses, int n_loss, const float* scores, int n_scores, int B, double* state,
+                           dcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * HBM-resident training audio (data.py:68-143: resample, crop, noise = noisy - clean, three torch.stft calls per item on the
  * loader workers; dcsnet/audio_store.py), audio_store.hip.
  * dcs_resample_sinc_f32: torchaudio.transforms.Resample(orig * g, new_ * g) of torchaudio 0.9.0 (sinc_interpolation, lowpass

@@ -3,6 +3,7 @@
     python tools/train.py dcs --clean-dir clean/ --noisy-dir noisy/ --out runs/dcs
     python tools/train.py dcs --clean-dir clean/ --noisy-dir noisy/ --out runs/dcs --resume auto      (continue a stopped run)
     python tools/train.py drs --clean-dir clean/ --noisy-dir noisy/ --out runs/drs --epochs 200 --batch 32
+    python tools/train.py dcs --clean-dir clean/ --noisy-dir noisy/ --out runs/dcs --validation device   (validate on the device)
 
 The mode comes first, as in the reference's `train.py dcs 0`: the model code reads it from sys.argv[1].  Files are paired by
 name (mono 16-bit PCM at config.file_sr).  The train / validation split follows the reference's data.py: a seeded shuffle of
@@ -56,6 +57,9 @@ def main():
     ap.add_argument('--val-split', type=float, default=80.0, help='percent of the files that train')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='activation storage (bf16: bf16 MFMA operands)')
     ap.add_argument('--no-graph', action='store_true')
+    ap.add_argument('--validation', default='host', choices=['host', 'device'],
+                    help="host: net.validation_step per batch (the reference's procedure); device: dcsnet.validation.DeviceValidator "
+                         '(losses, STOI and the epoch means on the device, one host read per epoch; val_pesq is NaN)')
     ap.add_argument('--device', default='cuda:0')
     a = ap.parse_args()
     if sys.argv[1] != a.mode:
@@ -81,7 +85,7 @@ def main():
     if a.dtype == 'bf16':
         net.set_activation_dtype('bf16')
     out = fit(net, stores[0], stores[1], a.out, a.epochs or config.max_epochs, a.batch or hparams['batch_size'],
-              use_graph=not a.no_graph, resume=a.resume)
+              use_graph=not a.no_graph, resume=a.resume, validation=a.validation)
     print(json.dumps({k: v for k, v in out.items() if k not in ('step', 'swa')}))
 
 
