@@ -1,5 +1,5 @@
-"""How good is an enhanced recording: STOI, SI-SNR and (on request) ESTOI, segmental SNR, LLR and cepstrum distance of whole
-recordings, scored where the Enhancer leaves them.
+"""How good is an enhanced recording: STOI, SI-SNR and (on request) ESTOI, segmental SNR, LLR, cepstrum distance, WSS and
+frequency-weighted segmental SNR of whole recordings, scored where the Enhancer leaves them.
 
     scorer = RecordingScorer(Enhancer(net, mode='dcs'))          (or a MagnitudeEnhancer)
     scores = scorer.score(noisy_waves, clean_waves, sample_rate=48000)
@@ -12,14 +12,17 @@ recordings, scored where the Enhancer leaves them.
     scorer.frame_measures = True                                  the dict gains 'ssnr', 'llr', 'cd' and their _noisy twins:
         segmental SNR (dB), LPC log-likelihood ratio and LPC cepstrum distance (Hu & Loizou; metrics.frame_measures), at
         config.sr, from two more calls (metrics.frame_measures_ragged, csrc/frame_measures.hip)
+    scorer.spectral_measures = True                               the dict gains 'wss', 'fwssnr' and their _noisy twins: weighted
+        spectral slope and frequency-weighted segmental SNR (dB) (Hu & Loizou; metrics.spectral_measures), at config.sr, from
+        two more calls (metrics.spectral_measures_ragged, csrc/spectral_measures.hip)
 
 The Enhancer keeps everything ragged in one flat device buffer with an int64 offset table; the metrics speak the same
 convention (metrics.stoi_ragged / sisnr_ragged, csrc/stoi_ragged.hip), so a whole test set is scored in a handful of launches
 and nothing returns to the host before the caller asks for values.  Per call: enhancer.enhance_segments and stitch make the
 flat speech estimate; the clean recordings go through the same upload and the same ops.resample_sinc into a store of the
 scorer's own, at the plan's offsets; the estimate and the enhancer's resident (resampled) noisy signal are scored against it.
-summarise() takes its columns from the dict it is given.  PESQ, WSS and the composite measures (CSIG / CBAK / COVL) are not
-computed."""
+summarise() takes its columns from the dict it is given.  PESQ is not computed; with PESQ values from elsewhere,
+metrics.composite_measures gives CSIG / CBAK / COVL (tools/evaluate.py --pesq-csv)."""
 import numpy as np
 import torch
 
@@ -31,12 +34,14 @@ from .enhance import Enhancer, read_pcm16
 class RecordingScorer:
     """enhancer: an Enhancer or a MagnitudeEnhancer, used as it is configured (mode, segment geometry, graph).  extended: score
     ESTOI as well.  The attribute frame_measures (default False; the constructor keeps its two arguments): score segmental SNR,
-    LLR and cepstrum distance as well.  self.metrics names the dict's keys: METRICS, then EXTENDED, then FRAME_MEASURES where
-    asked for."""
+    LLR and cepstrum distance as well.  The attribute spectral_measures (default False, likewise): score WSS and the
+    frequency-weighted segmental SNR as well.  self.metrics names the dict's keys: METRICS, then EXTENDED, then FRAME_MEASURES,
+    then SPECTRAL_MEASURES where asked for."""
 
     METRICS = ('stoi', 'stoi_noisy', 'sisnr', 'sisnr_noisy')
     EXTENDED = ('estoi', 'estoi_noisy')
     FRAME_MEASURES = ('ssnr', 'ssnr_noisy', 'llr', 'llr_noisy', 'cd', 'cd_noisy')
+    SPECTRAL_MEASURES = ('wss', 'wss_noisy', 'fwssnr', 'fwssnr_noisy')
 
     def __init__(self, enhancer, extended=False):
         if not isinstance(enhancer, Enhancer):
@@ -44,12 +49,14 @@ class RecordingScorer:
         self.enhancer = enhancer
         self.extended = bool(extended)
         self.frame_measures = False                          # set it to True on the scorer: the constructor's arguments are pinned
+        self.spectral_measures = False                       # likewise
         self._clean = None                                   # the clean recordings at config.sr, capacity kept across calls
 
     @property
     def metrics(self):
         return (self.METRICS + (self.EXTENDED if self.extended else ()) +
-                (self.FRAME_MEASURES if self.frame_measures else ()))
+                (self.FRAME_MEASURES if self.frame_measures else ()) +
+                (self.SPECTRAL_MEASURES if self.spectral_measures else ()))
 
     @staticmethod
     def _check_pairs(noisy_waves, clean_waves):
@@ -96,6 +103,11 @@ class RecordingScorer:
             unprocessed = metrics.frame_measures_ragged(clean, noisy, offsets, enh.sr, longest=longest)
             for k in ('ssnr', 'llr', 'cd'):                  # the order of FRAME_MEASURES
                 scores[k], scores[k + '_noisy'] = enhanced[k], unprocessed[k]
+        if self.spectral_measures:
+            enhanced = metrics.spectral_measures_ragged(clean, speech, offsets, enh.sr, longest=longest)
+            unprocessed = metrics.spectral_measures_ragged(clean, noisy, offsets, enh.sr, longest=longest)
+            for k in ('wss', 'fwssnr'):                      # the order of SPECTRAL_MEASURES
+                scores[k], scores[k + '_noisy'] = enhanced[k], unprocessed[k]
         if return_audio:
             return scores, enh._split(plan, speech)
         return scores
@@ -117,7 +129,9 @@ def summarise(scores):
     the dict ('estoi', 'estoi_noisy'): their columns behind the four, [n, 6], and estoi_improvement in the summary.  With the
     frame-measure keys in the dict (RecordingScorer.FRAME_MEASURES): their six columns behind those, and ssnr_improvement
     (enhanced - noisy, as for the others), llr_improvement and cd_improvement — these two are noisy - enhanced, because a
-    lower LLR or cepstrum distance is the better one, so a positive improvement always means the network helped."""
+    lower LLR or cepstrum distance is the better one, so a positive improvement always means the network helped.  With the
+    spectral-measure keys in the dict (RecordingScorer.SPECTRAL_MEASURES): their four columns behind those, wss_improvement
+    (noisy - enhanced: lower is better) and fwssnr_improvement (enhanced - noisy)."""
     keys = RecordingScorer.METRICS
     extended = all(k in scores for k in RecordingScorer.EXTENDED)
     if extended:
@@ -125,6 +139,9 @@ def summarise(scores):
     measures = all(k in scores for k in RecordingScorer.FRAME_MEASURES)
     if measures:
         keys = keys + RecordingScorer.FRAME_MEASURES
+    spectral = all(k in scores for k in RecordingScorer.SPECTRAL_MEASURES)
+    if spectral:
+        keys = keys + RecordingScorer.SPECTRAL_MEASURES
     table = torch.stack([scores[k].to(torch.float32) for k in keys], dim=1).cpu().numpy()
 
     def mean(v):
@@ -144,4 +161,8 @@ def summarise(scores):
         out['ssnr_improvement'] = mean(table[:, j] - table[:, j + 1])
         out['llr_improvement'] = mean(table[:, j + 3] - table[:, j + 2])
         out['cd_improvement'] = mean(table[:, j + 5] - table[:, j + 4])
+    if spectral:
+        j = keys.index('wss')
+        out['wss_improvement'] = mean(table[:, j + 1] - table[:, j])
+        out['fwssnr_improvement'] = mean(table[:, j + 2] - table[:, j + 3])
     return out, table

@@ -39,8 +39,14 @@ to [0, 10], each averaged over the 95 % smallest frame values), at the signals' 
 PARITY UNPINNED: neither pysepm nor the MATLAB originals are here to compare with; the tests check the defining properties and
 independent routes only (tests/test_frame_measures_cpu.py).  On the device it is `frame_measures_ragged()`
 (csrc/frame_measures.hip: fp64 until the final rounding; `frame_measures()` is its numerics contract,
-tests/test_frame_measures_device.py).  WSS and the composite measures (CSIG / CBAK / COVL) are not restated: the composites
-need PESQ, and WSS a filter-bank table that nothing here can verify.
+tests/test_frame_measures_device.py).
+
+WSS, fwSegSNR, composites.  `spectral_measures()` restates the weighted spectral slope and the frequency-weighted segmental
+SNR of the same paper after `comp_wss.m` / `comp_fwseg.m`: the frame measures' framing, a zero-padded FFT, 25 Gaussian-shaped
+critical bands.  PARITY UNPINNED for the same reason (tests/test_spectral_measures_cpu.py: defining properties and
+independent routes).  On the device it is `spectral_measures_ragged()` (csrc/spectral_measures.hip, an fp64 FFT in LDS;
+tests/test_spectral_measures_device.py).  `composite_measures()` is Hu & Loizou's CSIG / CBAK / COVL regression on PESQ,
+LLR, WSS and segmental SNR; the PESQ values come from the caller.
 
 PESQ.  ITU-T P.862 is ~2 k lines of reference C with psychoacoustic tables; it is not restated.  `pesq` stays the
 imported package when present, else None (calc_metric then reports NaN, as in round 1)."""
@@ -467,3 +473,204 @@ def frame_measures_ragged(clean, estimate, offsets, fs, longest=None):
     clean, estimate, offsets, _ = _ragged_args('frame_measures_ragged', clean, estimate, offsets, longest)
     s, l, c = ops.frame_measures_ragged(clean, estimate, offsets, fs)
     return {'ssnr': s, 'llr': l, 'cd': c}
+
+
+# ---- weighted spectral slope, frequency-weighted segmental SNR, the composite measures (Hu & Loizou) ----------------------------
+
+CRIT_CENTRES = np.array([50.0, 120.0, 190.0, 260.0, 330.0, 400.0, 470.0, 540.0, 617.372, 703.378, 798.717, 904.128, 1020.38,
+                         1148.30, 1288.72, 1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97, 2978.04, 3276.17,
+                         3597.63])                            # Hz
+CRIT_BANDWIDTHS = np.array([70.0] * 7 + [77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914, 140.423, 153.823, 168.154,
+                                         183.457, 199.776, 217.153, 235.631, 255.255, 276.072, 298.126, 321.465, 346.136])
+NUM_CRIT = 25
+CRIT_MIN_FACTOR = float(np.exp(-30.0 / (2.0 * 2.303)))      # band weights at or below it are 0
+WSS_FLOOR = 1e-10                                             # of a band's power, before the logarithm
+FWSSNR_RANGE = (-10.0, 35.0)                                  # dB, per frame
+FWSSNR_GAMMA = 0.2
+
+
+def spectral_fft_size(fs):
+    """The smallest power of two >= 2 N, N = round(0.03 fs): 512 at 8 kHz, 1024 at 16 kHz, 2048 at 22.05 kHz, 4096 at 48 kHz."""
+    nfft = 1
+    while nfft < 2 * frame_geometry(fs)[0]:
+        nfft *= 2
+    return nfft
+
+
+def critical_band_bank(fs, nfft=None):
+    """g [25, H], H = nfft / 2: band i is exp(-11 ((j - f0) / bw)^2 + ln 70 - ln bandwidth_i) over the bins j, with
+    f0 = floor(centre_i / (fs / 2) H) and bw = bandwidth_i / (fs / 2) H, and 0 wherever that does not exceed CRIT_MIN_FACTOR."""
+    H = (spectral_fft_size(fs) if nfft is None else int(nfft)) // 2
+    half = float(fs) / 2.0
+    f0 = np.floor(CRIT_CENTRES / half * H)
+    bw = CRIT_BANDWIDTHS / half * H
+    j = np.arange(H, dtype=np.float64)
+    g = np.exp(-11.0 * ((j[None, :] - f0[:, None]) / bw[:, None]) ** 2 + (np.log(70.0) - np.log(CRIT_BANDWIDTHS))[:, None])
+    g[g <= CRIT_MIN_FACTOR] = 0.0
+    return g
+
+
+def compact_bank(g):
+    """The bank's non-zero runs: (first int32 [25], offset int32 [26], weights float64 [offset[25]]); band i is
+    g[i, first[i]:first[i] + offset[i + 1] - offset[i]] == weights[offset[i]:offset[i + 1]], and 0 elsewhere."""
+    first, offset, weights = [], [0], []
+    for row in g:
+        nz = np.flatnonzero(row)
+        a, b = (int(nz[0]), int(nz[-1]) + 1) if len(nz) else (0, 0)
+        assert len(nz) == b - a, 'a band is one contiguous run of bins'
+        first.append(a)
+        offset.append(offset[-1] + b - a)
+        weights.append(row[a:b])
+    return np.array(first, dtype=np.int32), np.array(offset, dtype=np.int32), np.concatenate(weights)
+
+
+def _nearest_peaks(e):
+    """The published search for the band energy of the nearest spectral peak: e [F, 25] dB -> peak [F, 24], one per slope
+    s_i = e_{i+1} - e_i.  Rising (s_i > 0): n = i, advance n while n < 24 and s_n > 0, peak_i = e_{n-1} — the band BELOW the one
+    the search stops at: the published code's off-by-one, kept.  Otherwise: n = i, step n down while n >= 0 and s_n <= 0,
+    peak_i = e_{n+1}."""
+    e = np.asarray(e, dtype=np.float64)
+    F, rows = e.shape[0], np.arange(e.shape[0])
+    s = e[:, 1:] - e[:, :-1]
+    peak = np.empty((F, NUM_CRIT - 1))
+    for i in range(NUM_CRIT - 1):
+        rising = s[:, i] > 0
+        up = np.full(F, i)
+        down = np.full(F, i)
+        for _ in range(NUM_CRIT):
+            go = rising & (up < NUM_CRIT - 1)
+            go[go] = s[rows[go], up[go]] > 0
+            up = up + go
+            go = ~rising & (down >= 0)
+            go[go] = s[rows[go], down[go]] <= 0
+            down = down - go
+        peak[:, i] = np.where(rising, e[rows, np.maximum(up - 1, 0)], e[rows, down + 1])
+    return peak
+
+
+def _wss_weights(e):
+    """W [F, 24] of one signal: 20 / (20 + max_k e_k - e_i) times 1 / (1 + peak_i - e_i)."""
+    peak = _nearest_peaks(e)
+    return (20.0 / (20.0 + np.max(e, axis=1, keepdims=True) - e[:, :-1])) * (1.0 / (1.0 + peak - e[:, :-1]))
+
+
+def spectral_frame_values(x, y, fs):
+    """The per-frame values of the clean signal x and the estimate y (1-D, equal length) at rate fs: (wss [F], fwssnr [F], valid
+    bool [F]); fwssnr is clamped and meaningful where valid (both magnitude spectra have a positive sum), wss is finite in
+    every frame."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if x.shape != y.shape or x.ndim != 1:
+        raise ValueError(f'spectral_measures: x {x.shape} and y {y.shape} must be 1-D signals of equal length')
+    N, S, _ = frame_geometry(fs)
+    F = frame_count(len(x), fs)
+    if F == 0:
+        return np.zeros(0), np.zeros(0), np.zeros(0, dtype=bool)
+    nfft = spectral_fft_size(fs)
+    H = nfft // 2
+    g = critical_band_bank(fs, nfft)
+    w = _measure_window(N)
+    wss, fw, valid = np.empty(F), np.zeros(F), np.zeros(F, dtype=bool)
+    for a in range(0, F, 2048):                              # bounded memory for long recordings
+        b = min(a + 2048, F)
+        idx = S * np.arange(a, b)[:, None] + np.arange(N)[None, :]
+        power, mag, energy = [], [], []
+        for sig in (x, y):
+            spec = np.fft.rfft(sig[idx] * w, n=nfft, axis=1)[:, :H]
+            p = spec.real ** 2 + spec.imag ** 2
+            power.append(p)
+            mag.append(np.sqrt(p))
+            energy.append(10.0 * np.log10(np.maximum(p @ g.T, WSS_FLOOR)))
+        ex, ey = energy
+        sx, sy = ex[:, 1:] - ex[:, :-1], ey[:, 1:] - ey[:, :-1]
+        W = 0.5 * (_wss_weights(ex) + _wss_weights(ey))
+        wss[a:b] = np.sum(W * (sx - sy) ** 2, axis=1) / np.sum(W, axis=1)
+        tx, ty = np.sum(mag[0], axis=1), np.sum(mag[1], axis=1)
+        ok = (tx > 0) & (ty > 0)
+        valid[a:b] = ok
+        with np.errstate(all='ignore'):
+            c = (mag[0][ok] / tx[ok, None]) @ g.T
+            p = (mag[1][ok] / ty[ok, None]) @ g.T
+            err = np.maximum((c - p) ** 2, EPS)
+            wgt = c ** FWSSNR_GAMMA
+            fw[a:b][ok] = np.clip(np.sum(wgt * 10.0 * np.log10(c * c / err), axis=1) / np.sum(wgt, axis=1), *FWSSNR_RANGE)
+    return wss, fw, valid
+
+
+def spectral_measures(x, y, fs):
+    """Weighted spectral slope (WSS) and frequency-weighted segmental SNR (fwSegSNR, dB) of the estimate y against the clean
+    signal x (1-D, equal length, both at rate fs), after Hu & Loizou's comp_wss.m / comp_fwseg.m -> {'wss', 'fwssnr'} as Python
+    floats.  The frame measures' framing (frame_geometry, frame_count, _measure_window); per frame |FFT(frame w, nfft)| on the
+    bins 0 .. nfft / 2 - 1, nfft = spectral_fft_size(fs); the 25 bands of critical_band_bank.  wss: band energies
+    e_i = 10 log10(max(sum |X|^2 g_i, 1e-10)), slopes s_i = e_{i+1} - e_i, weights from the distance to the largest band and
+    to the nearest peak (_nearest_peaks: the published rising search and its off-by-one are KEPT as published), averaged over
+    both signals; the frame value is sum W_i (s_i^x - s_i^y)^2 / sum W_i, and the score the mean of the
+    max(1, floor(0.95 F + 0.5)) smallest of ALL F frame values (the floor makes silence finite); NaN without a frame.  fwssnr:
+    magnitude spectra normalised to unit sum, band values c_i (clean) and p_i (estimate), frame value
+    sum c_i^0.2 10 log10(c_i^2 / max((c_i - p_i)^2, EPS)) / sum c_i^0.2 clamped to [-10, 35]; the score is the mean over the
+    frames where both magnitude sums are positive, NaN for none.  The formulae leave one case undefined and it is kept as it
+    falls: a band on which the clean magnitude is exactly 0 while the frame is not silent (band-limited synthetic input; no
+    signal with a noise floor) has c_i = 0, its term is 0 x log10(0) = NaN, and with it the frame's and the recording's
+    fwssnr — on the device as here.  PARITY UNPINNED (see the module docstring): neither the
+    MATLAB originals nor pysepm are here to compare with; tests/test_spectral_measures_cpu.py checks the defining properties
+    and independent routes."""
+    wss, fw, valid = spectral_frame_values(x, y, fs)
+    return {'wss': _trimmed_mean(wss), 'fwssnr': float(np.mean(fw[valid])) if valid.any() else float('nan')}
+
+
+def wss(x, y, fs):
+    """spectral_measures(x, y, fs)['wss']."""
+    return spectral_measures(x, y, fs)['wss']
+
+
+def fwssnr(x, y, fs):
+    """spectral_measures(x, y, fs)['fwssnr']."""
+    return spectral_measures(x, y, fs)['fwssnr']
+
+
+def composite_measures(pesq, llr, wss, ssnr):
+    """Hu & Loizou's composite measures from PESQ, LLR, WSS and segmental SNR -> {'csig', 'cbak', 'covl'} (signal distortion,
+    background intrusiveness, overall quality), each clamped to [1, 5].  Elementwise on numbers, numpy arrays or torch tensors
+    of any device."""
+    import torch
+    if any(isinstance(v, torch.Tensor) for v in (pesq, llr, wss, ssnr)):
+        def clamp(v):
+            return v.clamp(1.0, 5.0)
+    else:
+        pesq, llr, wss, ssnr = (np.asarray(v, dtype=np.float64) for v in (pesq, llr, wss, ssnr))
+
+        def clamp(v):
+            return np.clip(v, 1.0, 5.0)
+    return {'csig': clamp(3.093 - 1.029 * llr + 0.603 * pesq - 0.009 * wss),
+            'cbak': clamp(1.634 + 0.478 * pesq - 0.007 * wss + 0.063 * ssnr),
+            'covl': clamp(1.594 + 0.805 * pesq - 0.512 * llr - 0.007 * wss)}
+
+
+def spectral_tables(fs, device):
+    """What the device pass reads, on `device` (cached): (window float64 [N], band_first int32 [25], band_offset int32 [26],
+    band_weights float64, twiddles float64 [nfft, 2] = (cos, -sin)(2 pi m / nfft)); the window and the weights are the host
+    function's own bits."""
+    fs = int(fs)
+    key = ('spectral', fs, str(device))
+    t = _device_tables.get(key)
+    if t is None:
+        import torch
+        nfft = spectral_fft_size(fs)
+        first, offset, weights = compact_bank(critical_band_bank(fs, nfft))
+        angle = 2.0 * np.pi * np.arange(nfft) / nfft
+        twiddles = np.stack([np.cos(angle), -np.sin(angle)], axis=1)
+        t = (measure_window(fs, device),) + tuple(torch.from_numpy(np.ascontiguousarray(v)).to(device)
+                                                  for v in (first, offset, weights, twiddles))
+        _device_tables[key] = t
+    return t
+
+
+def spectral_measures_ragged(clean, estimate, offsets, fs, longest=None):
+    """spectral_measures(clean[a:b], estimate[a:b], fs) for every recording [a, b) = offsets[i:i + 2] of two flat device buffers
+    -> {'wss', 'fwssnr'}: float32 [n] device tensors (NaN where the host function has NaN), fp64 until that rounding, in three
+    launches whatever n is (csrc/spectral_measures.hip) and without a host read-back (capturable when offsets are on the
+    device).  At the signals' own rate fs, 8000 .. 48000 (DcsHipError otherwise).  offsets, longest: as for stoi_ragged (no grid
+    here depends on longest).  CPU signals raise DcsHipError."""
+    from . import ops
+    clean, estimate, offsets, _ = _ragged_args('spectral_measures_ragged', clean, estimate, offsets, longest)
+    w, f = ops.spectral_measures_ragged(clean, estimate, offsets, fs)
+    return {'wss': w, 'fwssnr': f}

@@ -1534,6 +1534,47 @@ def frame_measures_ragged(clean, est, offsets, fs, window=None, out=None, worksp
     return tuple(out)
 
 
+def spectral_measures_workspace_bytes(n, total, fs):
+    """The workspace of spectral_measures_ragged for n recordings of `total` samples together at rate fs (host arithmetic)."""
+    nbytes = _lib.load().dcs_spectral_measures_ragged_workspace_bytes(int(n), int(total), int(fs))
+    if nbytes < 0:
+        raise _lib.DcsHipError(f'spectral_measures_ragged: unsupported arguments ({n} recordings, {total} samples, fs={fs}; the '
+                               f'rate must lie in 8000 .. 48000)')
+    return nbytes
+
+
+def spectral_measures_ragged(clean, est, offsets, fs, out=None, workspace=None):
+    """Weighted spectral slope and frequency-weighted segmental SNR of n recordings of different lengths at their own rate fs
+    (8000 .. 48000): clean / est float [total], offsets int64 [n + 1] on the device -> (wss, fwssnr), float [n] each,
+    metrics.spectral_measures per recording in fp64 (dcs_spectral_measures_ragged_f32: three launches whatever n is).  The
+    window, the band table and the twiddles are metrics.spectral_tables(fs, device).  out (two float32 [n] tensors) and
+    workspace (uint8, at least spectral_measures_workspace_bytes) let a caller own the buffers the call writes."""
+    n, total = _chk_ragged('spectral_measures_ragged', offsets, clean, est)
+    dev = clean.device
+    fs = int(fs)
+    nbytes = spectral_measures_workspace_bytes(n, total, fs)
+    from .metrics import spectral_tables
+    window, band_first, band_offset, band_weights, twiddles = spectral_tables(fs, dev)
+    if out is None:
+        out = tuple(torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+    if len(out) != 2:
+        raise _lib.DcsHipError(f'spectral_measures_ragged: out must be two float32 [{n}] tensors on {dev}')
+    for o in out:
+        _chk(o, 'spectral_measures_ragged: out', 1)
+        if o.numel() != n or o.device != dev:
+            raise _lib.DcsHipError(f'spectral_measures_ragged: out must be two float32 [{n}] tensors on {dev}')
+    ws = _workspace(nbytes, dev) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
+        raise _lib.DcsHipError(f'spectral_measures_ragged: workspace must be a contiguous uint8 tensor on {dev}')
+    sig = (ptr(clean), ptr(est)) if total else (None, None)
+    check(_lib.load().dcs_spectral_measures_ragged_f32(*sig, ptr(offsets), n, total, fs, ptr(window), window.numel(),
+                                                       ptr(band_first), ptr(band_offset), ptr(band_weights),
+                                                       band_weights.numel(), ptr(twiddles), twiddles.shape[0], ptr(out[0]),
+                                                       ptr(out[1]), ptr(ws), ws.numel(), cur_stream()),
+          'dcs_spectral_measures_ragged_f32')
+    return tuple(out)
+
+
 # ---- HBM-resident training audio (csrc/audio_store.hip, dcsnet/audio_store.py) ----------------------------------------
 
 _SINC_LOWPASS_WIDTH, _SINC_ROLLOFF = 6, 0.99                 # torchaudio 0.9.0's Resample defaults (config.py:61)

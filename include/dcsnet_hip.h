@@ -952,6 +952,29 @@ int dcs_frame_measures_ragged_f32(const float* clean, const float* est, const lo
                                   void* workspace, long workspace_bytes, dcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Weighted spectral slope (WSS) and frequency-weighted segmental SNR (fwSegSNR) of whole recordings (Hu & Loizou's comp_wss /
+ * comp_fwseg as dcsnet/metrics.py::spectral_measures restates them: that host function is the numerics contract),
+ * spectral_measures.hip, in the ragged convention above with the frame measures' limits (n, total, 8000 <= fs <= 48000), framing
+ * and window.  nfft = the smallest power of two >= 2 N (512 .. 4096), H = nfft / 2 bins; 25 critical bands.
+ * dcs_spectral_measures_ragged_workspace_bytes: pure host arithmetic, frame base long[n + 1] | per-frame values double[2][Fc] |
+ *   validity int[Fc], Fc = total / S; < 0 for bad arguments (Fc must stay below 2^31).
+ * dcs_spectral_measures_ragged_f32: out_wss / out_fwssnr float[n]: the mean of the K = max(1, floor(0.95 F + 0.5)) smallest WSS
+ *   values of ALL F frames, and the mean of the fwSegSNR (clamped to [-10, 35] dB) over the frames where both magnitude
+ *   spectra have a positive sum; NaN without such frames.  Device tables, all from metrics.spectral_tables:
+ *   window double[window_len = N]; the bank as band_first int[25] (a band's first bin), band_offset int[26] (where its
+ *   weights start in band_weights: band i has band_offset[i + 1] - band_offset[i] of them) and band_weights
+ *   double[band_weights_len] (a kernel clamps what it reads from these three into the spectrum and the weights);
+ *   twiddles double[2 nfft]: (cos, -sin)(2 pi m / nfft), twiddles_len = nfft.  fp64 until the rounding to float at the end.
+ *   Three launches whatever n is; no atomics, no sync, no read-back (capturable, bit-reproducible); a recording's scores do
+ *   not depend on the other recordings of the call. */
+long dcs_spectral_measures_ragged_workspace_bytes(int n, long total, int fs);
+int dcs_spectral_measures_ragged_f32(const float* clean, const float* est, const long* offsets, int n, long total, int fs,
+                                     const double* window, int window_len, const int* band_first, const int* band_offset,
+                                     const double* band_weights, int band_weights_len, const double* twiddles, int twiddles_len,
+                                     float* out_wss, float* out_fwssnr, void* workspace, long workspace_bytes,
+                                     dcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * The books of a validation epoch on the device (dcsnet/validation.py), validation.hip: one launch per batch folds the batch
  * into `state`, so an epoch ends with one host read.  losses: device float[n_loss], n_loss = 3 (noise, speech, total) or 1
  * (speech); the MONITORED loss is losses[n_loss - 1].  scores: device float[n_scores][B], 0 <= n_scores <= DCS_VAL_MAX_SCORES,

@@ -17,8 +17,13 @@ distance; csrc/frame_measures.hip) on the same seeded set beside the STOI pass, 
 the wall-clock time of the host function metrics.frame_measures over the set and the largest device - host differences ->
 profiles/frame_measures_bench.json.
 
+--spectral-measures does the same for metrics.spectral_measures_ragged (WSS, frequency-weighted segmental SNR;
+csrc/spectral_measures.hip): its device pass beside the STOI pass and the frame-measures pass, the three alternating in the same
+rounds, the host function metrics.spectral_measures and the largest differences -> profiles/spectral_measures_bench.json.
+
 usage: python tools/score_bench.py [--out profiles/score_bench.json] [--recordings 32] [--extended] [--parent-json FILE]
-       python tools/score_bench.py --frame-measures [--out profiles/frame_measures_bench.json] [--recordings 32]"""
+       python tools/score_bench.py --frame-measures [--out profiles/frame_measures_bench.json] [--recordings 32]
+       python tools/score_bench.py --spectral-measures [--out profiles/spectral_measures_bench.json] [--recordings 32]"""
 import argparse
 import json
 import os
@@ -114,12 +119,65 @@ def frame_measures_bench(a, c, e, off, off_h, longest, fs):
     return res
 
 
+def spectral_measures_bench(a, c, e, off, off_h, longest, fs):
+    """The device pass of WSS and fwSegSNR beside the STOI pass and the frame-measures pass, and the host function on the same
+    set."""
+    n = a.recordings
+    spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
+    methods = (('stoi_ragged_call', lambda: metrics.stoi_ragged(c, e, off, fs, longest=longest)),
+               ('frame_measures_ragged_call', lambda: metrics.frame_measures_ragged(c, e, off, fs, longest=longest)),
+               ('spectral_measures_ragged_call', lambda: metrics.spectral_measures_ragged(c, e, off, fs, longest=longest)))
+    first = {}
+    for name, fn in methods:
+        first[name] = fn()
+        torch.cuda.synchronize()
+    times = timed_rounds(methods, a.min_seconds)
+    ch, eh = c.cpu().numpy(), e.cpu().numpy()
+    t0 = time.perf_counter()
+    host = [metrics.spectral_measures(ch[p:q], eh[p:q], fs) for p, q in spans]
+    host_s = time.perf_counter() - t0
+    N, S, _ = metrics.frame_geometry(fs)
+    nfft = metrics.spectral_fft_size(fs)
+    res = {'metric': 'spectral_measures_recordings', 'device': torch.cuda.get_device_name(0), 'recordings': n,
+           'audio_seconds': round(float(off_h[-1]) / fs, 2), 'lengths_s': '1 .. 10 s at 16 kHz, uniform, seeded',
+           'frames': int(sum(metrics.frame_count(q - p, fs) for p, q in spans)), 'frame': {'N': N, 'S': S, 'nfft': nfft},
+           'first_measurement': 'no earlier figure exists for this pass on the MI355X and nothing at the parent commit compares',
+           'timing': 'device events around one pass over the set; the three device methods alternate in 3 rounds, each filling a '
+                     'third of min_seconds with repeated passes; median over the passes.  host: wall clock of one loop of '
+                     'metrics.spectral_measures over the set (numpy, fp64), signals already on the host',
+           'min_seconds': a.min_seconds,
+           'kernel_launches': {'spectral_measures_ragged_call': 3, 'frame_measures_ragged_call': 3, 'stoi_ragged_call': 2 * 2 + 4,
+                               'stoi_ragged_call_fills': 2},
+           'workspace_bytes': int(ops.spectral_measures_workspace_bytes(n, int(off_h[-1]), fs)),
+           'frame_kernel_lds_bytes_derived': 16 * nfft, 'host_loop_s': round(host_s, 4),
+           'derived': 'frame_kernel_lds_bytes_derived is 16 nfft, what the launch passes as dynamic LDS (the kernel has no static '
+                      'LDS), not a reading of the code object',
+           'differences': 'this set (harmonic signals) does not meet the input condition of '
+                          'tests/test_spectral_measures_device.py (every band slope above 1e-6 dB), and its WSS values are two '
+                          'orders larger than that test\'s: the differences below are float32 roundings of those values and '
+                          'are not to be read against profiles/spectral_measures_parity.json'}
+    for name, _ in methods:
+        res[name] = pass_stats(times[name], n)
+    ms = res['spectral_measures_ragged_call']['ms_per_pass_median']
+    res['spectral_measures_over_stoi_pass'] = round(ms / res['stoi_ragged_call']['ms_per_pass_median'], 3)
+    res['spectral_measures_over_frame_measures_pass'] = round(ms / res['frame_measures_ragged_call']['ms_per_pass_median'], 3)
+    res['host_loop_over_device_pass'] = round(host_s * 1e3 / ms, 1)
+    for k in ('wss', 'fwssnr'):
+        res[f'{k}_max_abs_diff_vs_host'] = float(np.nanmax(np.abs(first['spectral_measures_ragged_call'][k].cpu().numpy() -
+                                                                  np.array([m[k] for m in host]))))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None, help='default: profiles/score_bench.json (--frame-measures: '
-                                                'profiles/frame_measures_bench.json); - for none')
+                                                'profiles/frame_measures_bench.json, --spectral-measures: '
+                                                'profiles/spectral_measures_bench.json); - for none')
     ap.add_argument('--frame-measures', action='store_true',
                     help='time metrics.frame_measures_ragged beside the STOI pass and the host function instead')
+    ap.add_argument('--spectral-measures', action='store_true',
+                    help='time metrics.spectral_measures_ragged beside the STOI pass, the frame-measures pass and the host function '
+                         'instead')
     ap.add_argument('--recordings', type=int, default=32)
     ap.add_argument('--min-seconds', type=float, default=1.0)
     ap.add_argument('--seed', type=int, default=0)
@@ -127,7 +185,8 @@ def main():
     ap.add_argument('--parent-json', default=None, help="this tool's JSON of the parent commit, same box, same session")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'frame_measures_bench.json' if a.frame_measures else 'score_bench.json')
+        a.out = os.path.join(ROOT, 'profiles', 'spectral_measures_bench.json' if a.spectral_measures else
+                             'frame_measures_bench.json' if a.frame_measures else 'score_bench.json')
     dev = torch.device('cuda:0')
     fs = 16000
     clean, est = synthetic_set(a.recordings, a.seed, fs)
@@ -138,6 +197,8 @@ def main():
     off = torch.from_numpy(off_h).to(dev)
     longest = int(np.diff(off_h).max())
     spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
+    if a.spectral_measures:
+        return write_result(spectral_measures_bench(a, c, e, off, off_h, longest, fs), a.out)
     if a.frame_measures:
         return write_result(frame_measures_bench(a, c, e, off, off_h, longest, fs), a.out)
 
