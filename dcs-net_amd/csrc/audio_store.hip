@@ -19,20 +19,16 @@
 //                               (fft512.hip, through fft512_common.h) and stft_bins_kernel in the same order, so the result is
 //                               bit for bit what frontend.stft_batch makes of the cropped waveforms.
 //
-// audio_stft_batch_kernel: a workgroup owns kFrames consecutive frames of one item; for each of the three signals in turn every wave
+// audio_stft_batch_kernel (its body: audio_batch_common.h, shared with audio_mix.hip): a workgroup owns kFrames consecutive frames of one item; for each of the three signals in turn every wave
 // transforms kFrames / 4 of them (frames held transformed in LDS, one padded row per frame), then the workgroup writes the 256
 // bins x kFrames frames as runs of kFrames * 8 bytes along T.  The index and start of an item are read from device memory (a
 // captured graph replays with what the host wrote there since); an index outside [0, n_items) or a start whose crop would leave
 // the utterance yields zeros for that item, so no value in those buffers makes the kernel read outside the store.
-#include "fft512_common.h"
-
-#ifndef DCS_AUDIO_FRAMES_PER_WG
-#define DCS_AUDIO_FRAMES_PER_WG 8
-#endif
+#include "audio_batch_common.h"
 
 namespace {
 
-using namespace dcs_fft512;
+using namespace dcs_audio_batch;
 
 // x float[x_off[rows]] (ragged rows) -> y float[y_off[rows]]; y_off[r + 1] - y_off[r] = ceil(n (x_off[r + 1] - x_off[r]) / o)
 __global__ __launch_bounds__(256) void resample_sinc_kernel(const float* __restrict__ x, const long* __restrict__ x_off,
@@ -59,16 +55,18 @@ __global__ __launch_bounds__(256) void resample_sinc_kernel(const float* __restr
     y[g] = acc;
 }
 
-constexpr int kFrames = DCS_AUDIO_FRAMES_PER_WG;              // frames per workgroup: bins stored as runs of kFrames * 8 B
-static_assert(kFrames % 4 == 0 && kFrames >= 8 && kFrames <= 32, "frames per workgroup: a multiple of 4 waves, runs >= 64 B");
-constexpr int kPitch = M + 32 / kFrames;                     // row pitch (float2): the bin reads below hit 64 distinct banks
-
-// torch.stft(center=True, pad_mode='reflect') index of a crop of L samples (L > 256: one reflection suffices)
-__device__ __forceinline__ int reflect_index(int n, int L) {
-    if (n < 0) n = -n;
-    if (n >= L) n = 2 * (L - 1) - n;
-    return n;
-}
+// the paired store's samples: clean and noisy at the same position of the same utterance, zero past its end (crop_batch)
+struct PairedSource {
+    const float* cs;
+    const float* ns;
+    long len;
+    int start;
+    __device__ __forceinline__ void load(int q, bool, float& c, float& y) const {
+        const long p = (long)start + q;
+        c = p < len ? cs[p] : 0.f;
+        y = p < len ? ns[p] : 0.f;
+    }
+};
 
 // grid (ceil(T / kFrames), B); outputs complex[B][256][T]
 __global__ __launch_bounds__(256) void audio_stft_batch_kernel(const float* __restrict__ clean, const float* __restrict__ noisy,
@@ -77,69 +75,10 @@ __global__ __launch_bounds__(256) void audio_stft_batch_kernel(const float* __re
                                                                const float* __restrict__ w, float2* __restrict__ out_noise,
                                                                float2* __restrict__ out_noisy, float2* __restrict__ out_clean,
                                                                int T, int hop, int L, float scale) {
-    __shared__ float2 tw[M], tw512[M];
-    __shared__ float2 fa[kFrames][kPitch];                   // frame t0 + slot of the current signal, transformed in place
-    __shared__ float2 fb[4][M];                              // a wave's second Stockham buffer
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long b = blockIdx.y;
-    const int t0 = (int)blockIdx.x * kFrames;
-    const int item = item_idx[b], start = item_start[b];
-    long base = 0, len = 0;
-    bool ok = item >= 0 && item < n_items && start >= 0;
-    if (ok) {
-        base = off[item];
-        len = off[item + 1] - base;
-        ok = start == 0 || (long)start + L <= len;           // crop_batch's starts: 0 when len <= L, else start + L < len
-    }
-    if (!ok) {                                               // (uniform over the workgroup: no barrier skipped by a part of it)
-        for (int e = threadIdx.x; e < M * kFrames; e += 256) {
-            const int t = t0 + e % kFrames, f = e / kFrames;
-            if (t < T) {
-                const long o = (b * M + f) * T + t;
-                out_noise[o] = out_noisy[o] = out_clean[o] = make_float2(0.f, 0.f);
-            }
-        }
-        return;
-    }
-    build_twiddles(tw, tw512);
-    const float* cs = clean + base;
-    const float* ns = noisy + base;
-#pragma unroll 1
-    for (int s = 0; s < 3; ++s) {                            // 0 clean, 1 noise = noisy - clean, 2 noisy (stft_frames_kernel's order)
-#pragma unroll 1
-        for (int i = 0; i < kFrames / 4; ++i) {
-            const int slot = wave * (kFrames / 4) + i, t = t0 + slot;
-            float2* a = fa[slot];
-            if (t < T) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int m = lane + 64 * r, k = 2 * m, n = t * hop + k - N / 2;
-                    const long p0 = (long)start + reflect_index(n, L), p1 = (long)start + reflect_index(n + 1, L);
-                    const float c0 = p0 < len ? cs[p0] : 0.f, c1 = p1 < len ? cs[p1] : 0.f;     // zero past the end (crop_batch)
-                    const float y0 = p0 < len ? ns[p0] : 0.f, y1 = p1 < len ? ns[p1] : 0.f;
-                    const float2 wk = *reinterpret_cast<const float2*>(w + k);
-                    float2 v;
-                    if (s == 0) v = make_float2(wk.x * c0, wk.y * c1);
-                    else if (s == 1) v = make_float2(wk.x * (y0 - c0), wk.y * (y1 - c1));
-                    else v = make_float2(wk.x * y0, wk.y * y1);
-                    a[m] = v;                                // (g[2m], g[2m + 1]): rfft512_kernel's load of the stored frame
-                }
-            }
-            __syncthreads();                                 // (first round: the twiddle tables as well)
-            fft256<false>(a, fb[wave], tw, lane);            // frames past T transform stale LDS: never stored below
-        }
-        // fft256 ends on a barrier: every transform of this signal is in fa
-        float2* out = s == 0 ? out_clean : (s == 1 ? out_noise : out_noisy);
-        for (int e = threadIdx.x; e < M * kFrames; e += 256) {
-            const int tt = e % kFrames, f = e / kFrames, t = t0 + tt;
-            if (t < T) {
-                const int k = f + 1;                         // the DC bin dropped (data.py:118)
-                const float2 v = k < M ? rfft512_bin(fa[tt], tw512, k) : rfft512_nyquist(fa[tt]);
-                out[(b * M + f) * T + t] = make_float2(v.x * scale, v.y * scale);      // stft_bins_kernel's scaling
-            }
-        }
-        __syncthreads();                                     // before the next signal's frames overwrite fa
-    }
+    const int start = item_start[blockIdx.y];
+    long base, len;
+    const bool ok = crop_of_item(off, n_items, item_idx[blockIdx.y], start, L, &base, &len);
+    stft_batch_body(PairedSource{clean + base, noisy + base, len, start}, ok, w, out_noise, out_noisy, out_clean, T, hop, L, scale);
 }
 
 }  // namespace

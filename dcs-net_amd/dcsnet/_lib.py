@@ -176,7 +176,10 @@ SIGNATURES = {
     'dcs_val_accumulate_f32': (_I, [_P, _I, _P, _I, _I, _P, _P]),
     'dcs_resample_sinc_f32':(_I, [_P, _P, _P, _P, _I, _L, _P, _I, _I, _I, _P]),
     'dcs_audio_stft_batch_f32': (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
-    'dcs_audio_stft_segments_f32': (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P, _P]),
+    'dcs_signal_power_ragged_f64': (_I, [_P, _P, _I, _L, _P, _P]),
+    'dcs_audio_mix_ragged_f32': (_I, [_P, _P, _I, _L, _P, _P, _I, _P, _P, _P, _P, _P]),
+    'dcs_audio_mix_stft_batch_f32': (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
+    'dcs_audio_stft_segments_f32':(_I, [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P, _P]),
     'dcs_segments_stitch_f32': (_I, [_P, _L, _P, _P, _I, _L, _I, _I, _I, _P, _P, _P]),
 }
 

@@ -1728,6 +1728,114 @@ def audio_stft_batch(clean, noisy, offsets, index, starts, window, T, hop, scale
     return out
 
 
+# ---- mixing a clean store and a noise store (csrc/audio_mix.hip, dcsnet/audio_store.py::MixingAudioStore) -----------------
+
+def signal_power_ragged(x, offsets):
+    """out float64 [n] (device): mean(x_i^2) of every recording x[offsets[i] : offsets[i + 1]] of a flat float32 store
+    (dcs_signal_power_ragged_f64).  offsets int64 [n + 1] on the device.  Squares and sums in fp64 in a fixed order: the same bits
+    on every run; an empty recording gives 0."""
+    _chk(x, 'x', 1)
+    _chk_index(offsets, 'offsets', torch.int64)
+    if offsets.numel() < 2 or offsets.device != x.device:
+        raise _lib.DcsHipError(f'signal_power_ragged: {offsets.numel()} offsets on {offsets.device} for x on {x.device}')
+    n = offsets.numel() - 1
+    out = torch.empty(n, dtype=torch.float64, device=x.device)
+    check(_lib.load().dcs_signal_power_ragged_f64(ptr(x), ptr(offsets), n, x.numel(), ptr(out), cur_stream()),
+          'dcs_signal_power_ragged_f64')
+    return out
+
+
+def _chk_mix_stores(what, clean, offsets, noise, noise_offsets):
+    _chk(clean, 'clean', 1)
+    _chk(noise, 'noise', 1)
+    _chk_index(offsets, 'offsets', torch.int64)
+    _chk_index(noise_offsets, 'noise_offsets', torch.int64)
+    if offsets.numel() < 2 or noise_offsets.numel() < 2:
+        raise _lib.DcsHipError(f'{what}: {offsets.numel()} offsets, {noise_offsets.numel()} noise offsets')
+    for t in (offsets, noise, noise_offsets):
+        if t.device != clean.device:
+            raise _lib.DcsHipError(f'{what}: every tensor on {clean.device}')
+
+
+def _chk_gain(t, B, dev):
+    _chk(t, 'gain', 1)
+    if t.numel() != B or t.device != dev:
+        raise _lib.DcsHipError(f'gain: expected a float32 tensor of {B} on {dev}, got {tuple(t.shape)} on {t.device}')
+
+
+def audio_mix_ragged(clean, offsets, noise, noise_offsets, noise_index, noise_start, gain, out=None):
+    """noisy float32 [N]: every whole recording of the flat clean store mixed with its draw (dcs_audio_mix_ragged_f32):
+    noisy_i[q] = clean_i[q] + gain[i] * noise_r[(noise_start[i] + q) mod len_r], r = noise_index[i], product and sum rounded to
+    float32 separately.  clean float32 [N] with offsets int64 [n + 1], noise float32 with noise_offsets int64 [n_noise + 1];
+    noise_index / noise_start int32 [n], gain float32 [n]; everything on the device, offsets[-1] = N (the caller's invariant).
+    An item whose draw cannot be followed (index or start out of range, an empty recording, a non-finite gain) gets
+    noisy = clean.  out: the destination (a contiguous float32 [N] tensor)."""
+    _chk_mix_stores('audio_mix_ragged', clean, offsets, noise, noise_offsets)
+    n = offsets.numel() - 1
+    _chk_index(noise_index, 'noise_index', torch.int32, n)
+    _chk_index(noise_start, 'noise_start', torch.int32, n)
+    dev = clean.device
+    _chk_gain(gain, n, dev)
+    _chk(out, 'out', 1)
+    if out is None:
+        out = torch.empty_like(clean)
+    elif out.shape != clean.shape or out.device != dev:
+        raise _lib.DcsHipError(f'audio_mix_ragged: out {tuple(out.shape)} on {out.device}, expected {tuple(clean.shape)} on {dev}')
+    for t in (noise_index, noise_start):
+        if t.device != dev:
+            raise _lib.DcsHipError(f'audio_mix_ragged: every tensor on {dev}')
+    check(_lib.load().dcs_audio_mix_ragged_f32(ptr(clean), ptr(offsets), n, clean.numel(), ptr(noise), ptr(noise_offsets),
+                                               noise_offsets.numel() - 1, ptr(noise_index), ptr(noise_start), ptr(gain), ptr(out),
+                                               cur_stream()), 'dcs_audio_mix_ragged_f32')
+    return out
+
+
+def audio_mix_stft_batch(clean, offsets, noise, noise_offsets, index, starts, noise_index, noise_start, gain, window, T, hop,
+                         scale, out=None):
+    """audio_stft_batch with the noisy signal mixed in the kernel (dcs_audio_mix_stft_batch_f32): item b is the crop
+    [starts[b], starts[b] + hop (T - 1)) of clean utterance index[b], and its noisy sample at utterance position q is
+    clean[q] + gain[b] * noise_r[(noise_start[b] + q) mod len_r], r = noise_index[b] (product and sum rounded to float32
+    separately; zero past the utterance's end).  clean / noise float32 stores with int64 offsets / noise_offsets on the device;
+    index / starts / noise_index / noise_start int32 [B], gain float32 [B] (device).  -> (noise, noisy, clean) complex64
+    [B, 256, T], noise = noisy - clean in the time domain: bit for bit audio_stft_batch on the store audio_mix_ragged writes
+    with the same draws.  An out-of-range index, start, noise index or noise start, an empty noise recording or a non-finite gain
+    gives zeros for that item.  out: as for audio_stft_batch."""
+    _chk_mix_stores('audio_mix_stft_batch', clean, offsets, noise, noise_offsets)
+    _chk(window, 'window', 1)
+    _chk_index(index, 'index', torch.int32)
+    B = index.numel()
+    _chk_index(starts, 'starts', torch.int32, B)
+    _chk_index(noise_index, 'noise_index', torch.int32, B)
+    _chk_index(noise_start, 'noise_start', torch.int32, B)
+    dev = clean.device
+    _chk_gain(gain, B, dev)
+    if window.numel() != 512:
+        raise _lib.DcsHipError(f'audio_mix_stft_batch: n_fft = 512 only, got a window of {window.numel()}')
+    T, hop = int(T), int(hop)
+    if B == 0 or B > 65535 or T < 2 or hop <= 0 or hop * (T - 1) <= 256:
+        raise _lib.DcsHipError(f'audio_mix_stft_batch: B={B}, T={T}, hop={hop} (need 1 <= B <= 65535, hop (T - 1) > 256)')
+    if out is None:
+        out = tuple(torch.empty((B, 256, T), dtype=torch.complex64, device=dev) for _ in range(3))
+    else:
+        out = tuple(out)
+        if len(out) != 3:
+            raise _lib.DcsHipError(f'audio_mix_stft_batch: out must hold (noise, noisy, clean), got {len(out)} tensors')
+        for name, t in zip(('noise', 'noisy', 'clean'), out):
+            if (t.dtype != torch.complex64 or tuple(t.shape) != (B, 256, T) or not t.is_contiguous() or
+                    t.device != dev):
+                raise _lib.DcsHipError(f'audio_mix_stft_batch: out[{name}] must be a contiguous complex64 [{B}, 256, {T}] on {dev}')
+    for t in (index, starts, noise_index, noise_start, window):
+        if t.device != dev:
+            raise _lib.DcsHipError(f'audio_mix_stft_batch: every tensor on {dev}')
+    noise_o, noisy_o, clean_o = out
+    check(_lib.load().dcs_audio_mix_stft_batch_f32(ptr(clean), ptr(offsets), offsets.numel() - 1, ptr(noise), ptr(noise_offsets),
+                                                   noise_offsets.numel() - 1, ptr(index), ptr(starts), ptr(noise_index),
+                                                   ptr(noise_start), ptr(gain), B, ptr(window), 512, T, hop, float(scale),
+                                                   ptr(noise_o), ptr(noisy_o), ptr(clean_o), cur_stream()),
+          'dcs_audio_mix_stft_batch_f32')
+    return out
+
+
 # ---- whole recordings in fixed-shape segments (csrc/enhance.hip, dcsnet/enhance.py) ------------------------------------
 
 def _chk_segment_geometry(what, T, overlap, hop, stitch):

@@ -1026,6 +1026,35 @@ int dcs_audio_stft_batch_f32(const float* clean, const float* noisy, const long*
                              float* out_noise, float* out_noisy, float* out_clean, dcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Mixing a clean-speech store and a noise store on the device (dcsnet/audio_store.py::MixingAudioStore), audio_mix.hip.
+ * Entry points added at ABI 20.  Both stores follow the resident-store convention above: float[offsets[n]] with int64
+ * offsets[n + 1] on the device.  The mixture rule: for a clean item of len_c samples, noise recording r of len_n >= 1 samples, a
+ * noise start s in [0, len_n) and a gain g, noisy[q] = clean[q] + g * noise_r[(s + q) mod len_n] for q < len_c — the noise
+ * loops and is aligned to the recording's sample 0; the product and the sum are rounded to float32 separately (no FMA) — and
+ * 0 for q >= len_c.  A draw is followed only if r is inside [0, n_noise), 1 <= len_n < 2^31, s is inside [0, len_n) and g is
+ * finite; no value in the per-item buffers makes a kernel read outside either store.
+ * dcs_signal_power_ragged_f64: out double[n] (device), out[i] = mean(x_i^2) of recording i = [offsets[i], offsets[i + 1])
+ *   clamped into [0, total); squares and sums in fp64 in a fixed order (the same bits on every run); 0 for an empty recording.
+ * dcs_audio_mix_ragged_f32: noisy float[total] = the mixture of every whole clean recording (total = offsets[n_items]) with the
+ *   draw noise_index / noise_start int[n_items], gain float[n_items] (device); an item whose draw is not followed gets
+ *   noisy = clean.  One thread per sample, plain stores.
+ * dcs_audio_mix_stft_batch_f32: dcs_audio_stft_batch_f32 with the noisy sample formed by the mixture rule at
+ *   q = item_start[b] + (position in the crop): out_noise / out_noisy / out_clean complex[B][256][T] are bit for bit what
+ *   dcs_audio_stft_batch_f32 gives on the store dcs_audio_mix_ragged_f32 writes with the same per-item draws.  item_index /
+ *   item_start / noise_index / noise_start int[B], gain float[B] on the device.  An item gets zeros if its index or start is
+ *   invalid by dcs_audio_stft_batch_f32's rule or its draw is not followed.  n_fft = 512 only, hop (T - 1) > 256.
+ * No sync; every call is capturable. */
+int dcs_signal_power_ragged_f64(const float* x, const long* offsets, int n, long total, double* out, dcs_stream_t stream);
+int dcs_audio_mix_ragged_f32(const float* clean, const long* offsets, int n_items, long total, const float* noise,
+                             const long* noise_offsets, int n_noise, const int* noise_index, const int* noise_start,
+                             const float* gain, float* noisy, dcs_stream_t stream);
+int dcs_audio_mix_stft_batch_f32(const float* clean, const long* offsets, int n_items, const float* noise,
+                                 const long* noise_offsets, int n_noise, const int* item_index, const int* item_start,
+                                 const int* noise_index, const int* noise_start, const float* gain, int B, const float* window,
+                                 int n_fft, int T, int hop, float scale, float* out_noise, float* out_noisy, float* out_clean,
+                                 dcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Whole recordings through a fixed-shape pass (dcsnet/enhance.py), enhance.hip (ABI 20).  A recording of len samples is
  * treated as zero-extended to L = hop (Tp - 1) samples, Tp = T + n (T - overlap) for the smallest n >= 0 with L >= len; it has
  * n + 1 segments of T frames, segment s at frame s (T - overlap) and at sample s (T - overlap) hop, hop (T - 1) samples long.

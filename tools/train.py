@@ -4,9 +4,13 @@
     python tools/train.py dcs --clean-dir clean/ --noisy-dir noisy/ --out runs/dcs --resume auto      (continue a stopped run)
     python tools/train.py drs --clean-dir clean/ --noisy-dir noisy/ --out runs/drs --epochs 200 --batch 32
     python tools/train.py dcs --clean-dir clean/ --noisy-dir noisy/ --out runs/dcs --validation device   (validate on the device)
+    python tools/train.py dcs --clean-dir clean/ --noise-dir noise/ --out runs/dcs                     (mix on the device)
+    python tools/train.py dcs --clean-dir clean/ --noise-dir noise/ --snr-range -5 20 --out runs/dcs
 
 The mode comes first, as in the reference's `train.py dcs 0`: the model code reads it from sys.argv[1].  Files are paired by
-name (mono 16-bit PCM at config.file_sr).  The train / validation split follows the reference's data.py: a seeded shuffle of
+name (mono 16-bit PCM at config.file_sr).  With --noise-dir instead of --noisy-dir there are no pairs: every training item is
+mixed on the device with a drawn noise recording, noise start and SNR (--snr-db levels, default 15,10,5,0, or --snr-range), by
+whole-recording mean powers; the validation files are mixed once, from a generator seeded by config.seed.  The train / validation split follows the reference's data.py: a seeded shuffle of
 the sorted file names, --val-split percent (80) for training; it is written to OUT/partition.json and reused on resume.
 OUT receives last.ckpt after every epoch, best.ckpt when the monitored value improved, metrics.jsonl, and final.ckpt — the SWA
 weights, the file tools/enhance.py and tools/evaluate.py should load — after the last epoch."""
@@ -45,11 +49,29 @@ def partition(clean_dir, noisy_dir, out_dir, val_split, seed):
     return part
 
 
-def main():
+def _snr_levels(text):
+    try:
+        levels = [float(v) for v in text.split(',')]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'{text!r}: comma-separated dB values expected, as in 15,10,5,0')
+    if not levels:
+        raise argparse.ArgumentTypeError('at least one SNR level')
+    return levels
+
+
+def parse_args(argv=None):
+    """The command line (argv: the arguments after the program name; default sys.argv[1:]); exits on a contradiction."""
+    argv = sys.argv[1:] if argv is None else list(argv)
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('mode', choices=MODES, help='dcs / dc: DCS-Net (C_NETWORK); drs / dr: DR-Net (R_NETWORK)')
     ap.add_argument('--clean-dir', required=True)
-    ap.add_argument('--noisy-dir', required=True)
+    ap.add_argument('--noisy-dir', default=None, help='the pre-mixed noisy files, paired with the clean ones by name')
+    ap.add_argument('--noise-dir', default=None,
+                    help='noise recordings instead of --noisy-dir: every training batch is mixed on the device at drawn SNRs '
+                         '(dcsnet.audio_store.MixingAudioStore); the validation part is mixed once, seeded by config.seed')
+    ap.add_argument('--snr-db', type=_snr_levels, default=None, help='with --noise-dir: the SNR levels to draw from (15,10,5,0)')
+    ap.add_argument('--snr-range', type=float, nargs=2, metavar=('LO', 'HI'), default=None,
+                    help='with --noise-dir: a uniform SNR in [LO, HI] dB instead of levels')
     ap.add_argument('--out', required=True, help='the run directory')
     ap.add_argument('--epochs', type=int, default=None, help='default: config.max_epochs')
     ap.add_argument('--batch', type=int, default=None, help='default: config.batch_size')
@@ -61,14 +83,34 @@ def main():
                     help="host: net.validation_step per batch (the reference's procedure); device: dcsnet.validation.DeviceValidator "
                          '(losses, STOI and the epoch means on the device, one host read per epoch; val_pesq is NaN)')
     ap.add_argument('--device', default='cuda:0')
-    a = ap.parse_args()
-    if sys.argv[1] != a.mode:
+    a = ap.parse_args(argv)
+    if not argv or argv[0] != a.mode:
         ap.error('the mode must be the first argument (the model code reads sys.argv[1])')
-    real = a.mode in ('drs', 'dr')
-    if real and a.dtype == 'bf16':
+    if (a.noisy_dir is None) == (a.noise_dir is None):
+        ap.error('exactly one of --noisy-dir (pre-mixed pairs) and --noise-dir (mix on the device) must be given')
+    if a.snr_db is not None and a.snr_range is not None:
+        ap.error('--snr-db and --snr-range exclude each other')
+    if a.noise_dir is None and (a.snr_db is not None or a.snr_range is not None):
+        ap.error('--snr-db / --snr-range need --noise-dir')
+    if a.snr_range is not None and not a.snr_range[0] <= a.snr_range[1]:
+        ap.error(f'--snr-range {a.snr_range[0]} {a.snr_range[1]}: LO must not exceed HI')
+    if a.mode in ('drs', 'dr') and a.dtype == 'bf16':
         ap.error(f'--dtype bf16 with {a.mode}: the real network has no bf16 activation storage')
+    return a
+
+
+def wav_names(directory):
+    names = sorted(f for f in os.listdir(directory) if f.lower().endswith('.wav'))
+    if not names:
+        raise SystemExit(f'{directory}: no .wav files')
+    return names
+
+
+def main():
+    a = parse_args()
+    real = a.mode in ('drs', 'dr')
     import torch
-    from dcsnet.audio_store import DeviceAudioStore
+    from dcsnet.audio_store import SNR_LEVELS_DB, DeviceAudioStore, MixingAudioStore
     from dcsnet.config import config, hparams
     from dcsnet.fit import fit
     if real:
@@ -76,11 +118,24 @@ def main():
     else:
         from dcsnet.c_network import C_NETWORK as Net
     os.makedirs(a.out, exist_ok=True)
-    part = partition(a.clean_dir, a.noisy_dir, a.out, a.val_split, config.seed)
+    # --noise-dir: the partition is over the clean files (they pair with themselves)
+    part = partition(a.clean_dir, a.noisy_dir or a.clean_dir, a.out, a.val_split, config.seed)
     dev = torch.device(a.device)
-    stores = [DeviceAudioStore.from_wav([os.path.join(a.clean_dir, f) for f in part[k]],
-                                        [os.path.join(a.noisy_dir, f) for f in part[k]], config, dev, ids=part[k])
-              for k in ('train', 'validation')]
+    if a.noise_dir is None:
+        stores = [DeviceAudioStore.from_wav([os.path.join(a.clean_dir, f) for f in part[k]],
+                                            [os.path.join(a.noisy_dir, f) for f in part[k]], config, dev, ids=part[k])
+                  for k in ('train', 'validation')]
+    else:
+        noise = wav_names(a.noise_dir)
+
+        def mixing(k):
+            return MixingAudioStore.from_wav([os.path.join(a.clean_dir, f) for f in part[k]],
+                                             [os.path.join(a.noise_dir, f) for f in noise], config, dev, ids=part[k],
+                                             noise_ids=noise, snr_db=a.snr_db or SNR_LEVELS_DB, snr_range=a.snr_range)
+        # validation is one fixed mixture per file, the same in every run and resume (its noise copy goes with the temporary);
+        # training mixes afresh in every batch
+        fixed = mixing('validation').materialise(generator=torch.Generator().manual_seed(int(config.seed)))
+        stores = [mixing('train'), fixed]
     net = Net(config, dict(hparams), config.seed).to(dev)
     if a.dtype == 'bf16':
         net.set_activation_dtype('bf16')
