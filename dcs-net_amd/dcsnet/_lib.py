@@ -18,6 +18,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_long
 _F = ctypes.c_float
+_D = ctypes.c_double
 _U64 = ctypes.c_ulonglong
 
 
@@ -177,6 +178,7 @@ SIGNATURES = {
     'dcs_resample_sinc_f32':(_I, [_P, _P, _P, _P, _I, _L, _P, _I, _I, _I, _P]),
     'dcs_audio_stft_batch_f32': (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
     'dcs_signal_power_ragged_f64': (_I, [_P, _P, _I, _L, _P, _P]),
+    'dcs_active_level_ragged_f64': (_I, [_P, _P, _I, _L, _I, _D, _P, _P, _P]),
     'dcs_audio_mix_ragged_f32': (_I, [_P, _P, _I, _L, _P, _P, _I, _P, _P, _P, _P, _P]),
     'dcs_audio_mix_stft_batch_f32': (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
     'dcs_audio_stft_segments_f32':(_I, [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P, _P]),

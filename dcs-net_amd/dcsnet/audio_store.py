@@ -259,9 +259,13 @@ class DeviceAudioStore:
 SNR_LEVELS_DB = (15, 10, 5, 0)                               # the levels VoiceBank+DEMAND's training set was mixed at
 
 
+LEVELS = ('power', 'p56')                                    # how a store measures a recording's level
+
+
 def mix_gain(clean_power, noise_power, snr_db):
-    """The gain g that puts g * noise at snr_db below the clean signal, by WHOLE-RECORDING mean powers (no active-speech-level
-    normalisation): sqrt(Pc / Pn) * 10 ** (-snr_db / 20), evaluated in float64 numpy and rounded once to float32 (a
+    """The gain g that puts g * noise at snr_db below the clean signal, given the LEVEL of each as a power — the whole-recording
+    mean square, or the ITU-T P.56 active power (MixingAudioStore's level= / noise_level=; the function is the same for
+    both): sqrt(Pc / Pn) * 10 ** (-snr_db / 20), evaluated in float64 numpy and rounded once to float32 (a
     numpy.float32 for scalars, a float32 array otherwise).  ValueError for a power that is zero, negative or not finite, a
     non-finite SNR, or a gain that float32 does not hold."""
     pc, pn, snr = (np.asarray(v, dtype=np.float64) for v in (clean_power, noise_power, snr_db))
@@ -321,20 +325,30 @@ def draw_mix(indices, noise_lengths, generator=None, snr_db=SNR_LEVELS_DB, snr_r
 class MixingAudioStore:
     """A clean-speech corpus and a noise corpus, both resident at config.sr, mixed per batch on the device:
     noisy[q] = clean[q] + g * noise_r[(s + q) mod len_r] with the recording r, the start s and the SNR drawn per item
-    (draw_mix) and g = mix_gain(power of the clean recording, power of the noise recording, SNR) — whole-recording mean
-    powers, not ITU-T P.56 active speech levels.  The noise loops and is aligned to the clean RECORDING's sample 0, so a crop
-    at start t hears noise_r[(s + t + ...) mod len_r]: what the crop of the materialised mixture holds.
+    (draw_mix) and g = mix_gain(level of the clean recording, level of the noise recording, SNR).  level / noise_level say
+    what a recording's level is, per side: 'power' (the default), its whole-recording mean square, or 'p56', its ITU-T P.56
+    active power (ops.active_level_ragged at config.sr, margin 15.9 dB: the mean square over the active part of the signal,
+    pauses left out — how VoiceBank+DEMAND was mixed).  The noise loops and is aligned to the clean RECORDING's sample 0, so a
+    crop at start t hears noise_r[(s + t + ...) mod len_r]: what the crop of the materialised mixture holds.
 
     clean / noise: lists of 1-D signals at config.file_sr (float32 or int16), uploaded and resampled as DeviceAudioStore does
     (upload_resampled).  snr_db: the levels to draw from; snr_range=(lo, hi): a uniform SNR instead.  clean_power / noise_power
-    (numpy float64, read back once) are the per-recording mean squares; a silent recording raises here and is named.
+    (numpy float64) are the per-recording mean squares, clean_level / noise_level what the gains use (the same arrays under
+    'power', the active powers under 'p56') and clean_activity / noise_activity the P.56 activity factors (NaN under 'power');
+    all are measured once, on the device, and read back in one transfer.  A silent recording raises here and is named, and so
+    does one without a P.56 level (an envelope that never reaches 2^-15 of full scale, or no margin crossing).  The level is
+    a property of the store, like the SNR choice: a resumed run must be given the same one.
 
     The duck type is DeviceAudioStore's (__len__, lengths, ids, T, crop_length, device, epoch, draw_starts, batch,
     batch_device), so fit, DeviceValidator and the SWA loop take it unchanged; materialise() gives a DeviceAudioStore with one
     fixed mixture per item, for validation and test sets."""
 
     def __init__(self, clean, noise, config, device, snr_db=SNR_LEVELS_DB, snr_range=None, ids=None, noise_ids=None,
-                 chunk_samples=1 << 24):
+                 chunk_samples=1 << 24, level='power', noise_level='power'):
+        for name, kind in (('level', level), ('noise_level', noise_level)):
+            if kind not in LEVELS:
+                raise ValueError(f'MixingAudioStore: {name}={kind!r}, expected one of {LEVELS}')
+        self.level_kind, self.noise_level_kind = level, noise_level
         clean, noise = list(clean), list(noise)
         if not clean or not noise:
             raise ValueError(f'MixingAudioStore: {len(clean)} clean and {len(noise)} noise recordings')
@@ -356,15 +370,34 @@ class MixingAudioStore:
             raise ValueError('MixingAudioStore: a recording of 2^31 samples or more')
         self.offsets = torch.from_numpy(off).to(self.device)
         self.noise_offsets = torch.from_numpy(noff).to(self.device)
-        power = torch.cat([ops.signal_power_ragged(self.clean, self.offsets),
-                           ops.signal_power_ragged(self.noise, self.noise_offsets)]).cpu().numpy()      # the one read-back
-        self.clean_power, self.noise_power = power[:len(clean)].copy(), power[len(clean):].copy()
-        for name, p, these in (('clean', self.clean_power, self.ids), ('noise', self.noise_power, self.noise_ids)):
-            silent = np.flatnonzero(~(p > 0))
-            if len(silent):
-                i = int(silent[0])
-                raise ValueError(f'MixingAudioStore: {name}[{i}]' + (f' ({these[i]})' if these is not None else '') +
-                                 ' is silent: no gain gives it an SNR')
+        sides = (('clean', self.clean, self.offsets, len(clean), level, self.ids),
+                 ('noise', self.noise, self.noise_offsets, len(noise), noise_level, self.noise_ids))
+        parts = [ops.signal_power_ragged(x, o) for _, x, o, _, _, _ in sides]
+        parts += [ops.active_level_ragged(x, o, self.sr).reshape(-1) for _, x, o, _, kind, _ in sides if kind == 'p56']
+        rest = torch.cat(parts).cpu().numpy()                                                            # the one read-back
+        power, levels, activity = [], [], []
+        for _, _, _, n, _, _ in sides:                           # the mean powers first ...
+            power.append(rest[:n].copy())
+            rest = rest[n:]
+        for k, (_, _, _, n, kind, _) in enumerate(sides):        # ... then (active_power, activity) rows of the 'p56' sides
+            if kind == 'p56':
+                levels.append(rest[0:2 * n:2].copy())
+                activity.append(rest[1:2 * n:2].copy())
+                rest = rest[2 * n:]
+            else:
+                levels.append(power[k])
+                activity.append(np.full(n, np.nan))
+        self.clean_power, self.noise_power = power
+        self.clean_level, self.noise_level = levels
+        self.clean_activity, self.noise_activity = activity
+        for k, (name, _, _, _, _, these) in enumerate(sides):
+            for p, why in ((power[k], ' is silent: no gain gives it an SNR'),
+                           (levels[k], ' has no ITU-T P.56 active speech level: its envelope never reaches the lowest threshold '
+                                       '(2^-15 of full scale), or its levels never cross the margin')):
+                bad = np.flatnonzero(~(p > 0))
+                if len(bad):
+                    i = int(bad[0])
+                    raise ValueError(f'MixingAudioStore: {name}[{i}]' + (f' ({these[i]})' if these is not None else '') + why)
         self.last_draws = None
         self._sel = torch.zeros(5 * 64, dtype=torch.int32, device=self.device)   # persistent [index | start | noise | nstart | gain]
 
@@ -395,7 +428,7 @@ class MixingAudioStore:
                 raise IndexError(f'MixingAudioStore: noise recording {r} out of range [0, {len(self.noise_lengths)})')
             if not 0 <= s < int(self.noise_lengths[r]):
                 raise IndexError(f'MixingAudioStore: noise start {s} outside recording {r} ({int(self.noise_lengths[r])} samples)')
-        gain = mix_gain(self.clean_power[idx], self.noise_power[noise_index], np.array(snr, dtype=np.float64))
+        gain = mix_gain(self.clean_level[idx], self.noise_level[noise_index], np.array(snr, dtype=np.float64))
         return noise_index, noise_start, snr, gain
 
     def _upload(self, ints, gain):

@@ -48,6 +48,12 @@ independent routes).  On the device it is `spectral_measures_ragged()` (csrc/spe
 tests/test_spectral_measures_device.py).  `composite_measures()` is Hu & Loizou's CSIG / CBAK / COVL regression on PESQ,
 LLR, WSS and segmental SNR; the PESQ values come from the caller.
 
+Active speech level.  `active_speech_level()` restates ITU-T P.56 method B after the published `asl_P56` of Hu & Loizou (two
+one-pole envelope smoothers, 15 power-of-two thresholds with a 0.2 s hangover, the 15.9 dB margin), taking the margin crossing
+itself where the published code bisects to 0.5 dB.  PARITY UNPINNED, as for STOI; tests/test_active_level_cpu.py checks the
+counts against a literal transcription of the published loop.  On the device it is ops.active_level_ragged
+(csrc/speech_level.hip, fp64; tests/test_active_level.py), which MixingAudioStore(level='p56') reads once per store.
+
 PESQ.  ITU-T P.862 is ~2 k lines of reference C with psychoacoustic tables; it is not restated.  `pesq` stays the
 imported package when present, else None (calc_metric then reports NaN, as in round 1)."""
 import numpy as np
@@ -674,3 +680,106 @@ def spectral_measures_ragged(clean, estimate, offsets, fs, longest=None):
     clean, estimate, offsets, _ = _ragged_args('spectral_measures_ragged', clean, estimate, offsets, longest)
     w, f = ops.spectral_measures_ragged(clean, estimate, offsets, fs)
     return {'wss': w, 'fwssnr': f}
+
+
+# ---- ITU-T P.56 active speech level (method B) -------------------------------------------------------------------------------------
+
+P56_T = 0.03                    # s, time constant of each of the two envelope smoothers
+P56_H = 0.2                     # s, hangover
+P56_THRESHOLDS = 15             # c[j] = 2 ** (j - 15): the 16-bit thresholds of the published code, on a full scale of 1
+P56_MARGIN_DB = 15.9
+
+
+def p56_hangover(fs):
+    """I = ceil(0.2 fs) samples, in integers."""
+    fs = int(fs)
+    if fs <= 0:
+        raise ValueError(f'p56_hangover: fs={fs}')
+    return -(-fs // 5)
+
+
+def p56_envelope(x, fs):
+    """q: |x| through the one-pole smoother g = exp(-1 / (0.03 fs)) twice, each from zero state (scipy.signal.lfilter, fp64)."""
+    from scipy.signal import lfilter
+    g = np.exp(-1.0 / (int(fs) * P56_T))
+    p = lfilter([1.0 - g], [1.0, -g], np.abs(np.asarray(x, dtype=np.float64)))
+    return lfilter([1.0 - g], [1.0, -g], p)
+
+
+def windowed_max(q, I):
+    """m[k] = max(q[max(0, k - I) .. k]) by block prefix and suffix maxima (van Herk) over blocks of I + 1 samples: exact."""
+    q = np.asarray(q, dtype=np.float64)
+    n, W = len(q), int(I) + 1
+    if n == 0:
+        return q.copy()
+    blocks = -(-n // W)
+    b = np.full(blocks * W, -np.inf)
+    b[:n] = q
+    b = b.reshape(blocks, W)
+    prefix = np.maximum.accumulate(b, axis=1).reshape(-1)[:n]
+    suffix = np.maximum.accumulate(b[:, ::-1], axis=1)[:, ::-1].reshape(-1)[:n]
+    m = prefix.copy()
+    if n > I:                                                # the window [k - I, k] lies in at most two blocks
+        m[I:] = np.maximum(prefix[I:], suffix[:n - I])
+    return m
+
+
+def p56_level(sq, n, counts, margin_db=P56_MARGIN_DB):
+    """(active_power, activity) from the sum of squares, the length and the 15 activity counts: the level arithmetic of
+    active_speech_level, in the order of operations the device kernel repeats."""
+    nan = (float('nan'), float('nan'))
+    if n == 0 or counts[0] == 0 or not np.isfinite(sq):
+        return nan
+    M = float(margin_db)
+    with np.errstate(all='ignore'):
+        a_prev = 10.0 * np.log10(sq / float(counts[0]))
+        d_prev = a_prev - 20.0 * np.log10(2.0 ** -15)
+        if d_prev < M:
+            return nan
+        for j in range(1, P56_THRESHOLDS):
+            if counts[j] == 0:
+                return nan
+            a_j = 10.0 * np.log10(sq / float(counts[j]))
+            d_j = a_j - 20.0 * np.log10(2.0 ** (j - 15))
+            if d_j <= M:
+                t = (d_prev - M) / (d_prev - d_j)
+                level_db = a_prev + t * (a_j - a_prev)
+                active = float(10.0 ** (level_db / 10.0))
+                return active, float((sq / n) / active)
+            a_prev, d_prev = a_j, d_j
+    return nan
+
+
+def active_speech_level(x, fs, margin_db=P56_MARGIN_DB):
+    """The ITU-T P.56 (method B) active speech level of the 1-D signal x at the integer rate fs, after the published asl_P56 of
+    Hu & Loizou with its 16-bit thresholds on a full scale of 1 -> {'active_power', 'activity', 'counts'}: the mean square over
+    the ACTIVE part of the signal, the share of it that is active (activity * active_power = mean(x^2)) and the 15 activity
+    counts (int64).  Host-side numpy / scipy in fp64.
+
+    q = |x| smoothed twice by y[k] = g y[k - 1] + (1 - g) u[k], g = exp(-1 / (0.03 fs)), from zero state.  counts[j] is the
+    number of samples k with max(q[max(0, k - I) .. k]) >= c[j] = 2 ** (j - 15), I = ceil(0.2 fs): the published hangover
+    counter (reset where q[k] >= c[j], counting while below I, expired at the start) in closed form; nothing is counted past
+    the end of the signal.  With A[j] = 10 log10(sum(x^2) / counts[j]) and D[j] = A[j] - 20 log10(c[j]), the level is where
+    D crosses the margin: for the first j >= 1 with D[j] <= margin_db, A is interpolated linearly in dB between j - 1 and j to
+    D = margin_db, and active_power = 10 ** (A / 10).  The published code bisects to within 0.5 dB of that crossing; this takes
+    the crossing itself, so the result carries no tolerance parameter.  Both values are NaN for an empty signal, a signal that
+    never reaches c[0] (counts[0] = 0), D[0] < margin_db, a sum of squares that is not finite, or no crossing before the
+    counts run out.
+
+    PARITY UNPINNED, as for STOI: no ITU or MATLAB implementation is here to compare with; tests/test_active_level_cpu.py
+    checks the counts against a literal transcription of the published loop and the defining properties.  On the device it is
+    ops.active_level_ragged (csrc/speech_level.hip); this function is its numerics contract (tests/test_active_level.py)."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 1:
+        raise ValueError(f'active_speech_level: expected a 1-D signal, got shape {x.shape}')
+    if int(fs) != fs or int(fs) <= 0:
+        raise ValueError(f'active_speech_level: fs={fs} must be a positive integer')
+    n = len(x)
+    counts = np.zeros(P56_THRESHOLDS, dtype=np.int64)
+    if n:
+        m = windowed_max(p56_envelope(x, fs), p56_hangover(fs))
+        counts[:] = [np.count_nonzero(m >= 2.0 ** (j - 15)) for j in range(P56_THRESHOLDS)]
+    with np.errstate(all='ignore'):
+        sq = float(np.sum(x * x))
+    active, activity = p56_level(sq, n, counts, margin_db)
+    return {'active_power': active, 'activity': activity, 'counts': counts}

@@ -1745,6 +1745,28 @@ def signal_power_ragged(x, offsets):
     return out
 
 
+ACTIVE_LEVEL_TILE = 4096                                     # samples per tile of csrc/speech_level.hip (256 threads x 16)
+
+
+def active_level_ragged(x, offsets, fs, margin_db=15.9, return_counts=False):
+    """The ITU-T P.56 active speech level of every recording x[offsets[i] : offsets[i + 1]] of a flat float32 store at the rate
+    fs (8000 .. 48000): out float64 [n, 2] (device) = (active_power, activity) per recording, metrics.active_speech_level in fp64
+    (dcs_active_level_ragged_f64: one launch, one workgroup per recording); NaN where that function has NaN.  offsets int64
+    [n + 1] on the device.  return_counts: also the 15 activity counts, int64 [n, 15].  The same bits on every run, with or
+    without the counts, and for a recording alone or among others."""
+    n, total = _chk_ragged('active_level_ragged', offsets, x)
+    fs = int(fs)
+    if not 8000 <= fs <= 48000:
+        raise _lib.DcsHipError(f'active_level_ragged: fs={fs}; the rate must lie in 8000 .. 48000')
+    if total == 0:
+        raise _lib.DcsHipError('active_level_ragged: an empty store')
+    out = torch.empty(n, 2, dtype=torch.float64, device=x.device)
+    counts = torch.empty(n, 15, dtype=torch.int64, device=x.device) if return_counts else None
+    check(_lib.load().dcs_active_level_ragged_f64(ptr(x), ptr(offsets), n, total, fs, float(margin_db), ptr(out), ptr(counts),
+                                                  cur_stream()), 'dcs_active_level_ragged_f64')
+    return (out, counts) if return_counts else out
+
+
 def _chk_mix_stores(what, clean, offsets, noise, noise_offsets):
     _chk(clean, 'clean', 1)
     _chk(noise, 'noise', 1)

@@ -1055,6 +1055,20 @@ int dcs_audio_mix_stft_batch_f32(const float* clean, const long* offsets, int n_
                                  dcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * ITU-T P.56 (method B) active speech level of every recording of a resident store, speech_level.hip (entry point added at
+ * ABI 20; dcsnet/metrics.py::active_speech_level is the numerics contract).  x float[total] with int64 offsets[n + 1] on the
+ * device, recording i = [offsets[i], offsets[i + 1]) clamped into [0, total); n <= 32767; fs in 8000 .. 48000.
+ * dcs_active_level_ragged_f64: out double[n][2] (device) = (active_power, activity) per recording: |x| smoothed twice by
+ *   y[k] = g y[k - 1] + (1 - g) u[k], g = exp(-1 / (0.03 fs)), from zero state; counts[j] = the number of samples whose last
+ *   ceil(0.2 fs) + 1 envelope values reach 2^(j - 15), j = 0 .. 14; the level where 10 log10(sum(x^2) / counts[j]) -
+ *   20 log10(2^(j - 15)) crosses margin_db, interpolated linearly in dB; activity = mean(x^2) / active_power.  Both are NaN for
+ *   an empty recording, one that never reaches 2^-15, or one without a crossing.  counts long[n][15] (device) receives the
+ *   activity counts; NULL: not written.  Everything in fp64, additions in a fixed order, no atomics: the same bits on every
+ *   run, and for a recording alone or among others.  One launch, no workspace, no sync; capturable. */
+int dcs_active_level_ragged_f64(const float* x, const long* offsets, int n, long total, int fs, double margin_db, double* out,
+                                long* counts, dcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Whole recordings through a fixed-shape pass (dcsnet/enhance.py), enhance.hip (ABI 20).  A recording of len samples is
  * treated as zero-extended to L = hop (Tp - 1) samples, Tp = T + n (T - overlap) for the smallest n >= 0 with L >= len; it has
  * n + 1 segments of T frames, segment s at frame s (T - overlap) and at sample s (T - overlap) hop, hop (T - 1) samples long.

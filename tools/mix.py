@@ -6,8 +6,8 @@
     python tools/evaluate.py --checkpoint final.ckpt testset/noisy testset/clean
 
 Input: mono 16-bit PCM WAV at config.file_sr.  Per clean file a noise recording, a noise start and an SNR are drawn from a
-generator seeded by --seed (default config.seed); the noise loops from its start and is scaled by whole-recording mean powers (no
-active-speech-level normalisation).  OUT/noisy/NAME and OUT/clean/NAME are written as mono 16-bit PCM at config.sr (the clean
+generator seeded by --seed (default config.seed); the noise loops from its start and is scaled by whole-recording mean powers, or
+with --level p56 / --noise-level p56 by ITU-T P.56 active speech levels (measured on the device).  OUT/noisy/NAME and OUT/clean/NAME are written as mono 16-bit PCM at config.sr (the clean
 file resampled, so every pair has one rate and one length: what tools/evaluate.py reads), and OUT/draws.csv holds one line per
 file: name, noise file, noise start (samples at config.sr), SNR in dB, gain, clipped-sample count of the mixture.  The conversion
 to PCM (x 32768, nearest, clipped to +-32767) runs on the host."""
@@ -21,6 +21,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'dcs-net_amd'))
+
+
+LEVELS = ('power', 'p56')                                    # dcsnet.audio_store.LEVELS
 
 
 def wav_names(directory):
@@ -53,6 +56,10 @@ def parse_args(argv=None):
     ap.add_argument('--out', required=True, help='receives noisy/, clean/ and draws.csv')
     ap.add_argument('--snr-db', type=_snr_levels, default=None, help='the SNR levels to draw from (default 15,10,5,0)')
     ap.add_argument('--snr-range', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='a uniform SNR in [LO, HI] dB')
+    ap.add_argument('--level', default='power', choices=LEVELS,
+                    help="what the SNR takes as the level of a clean recording: 'power', its whole-recording mean square, or 'p56', its "
+                         'ITU-T P.56 active speech level (pauses left out, as VoiceBank+DEMAND was mixed)')
+    ap.add_argument('--noise-level', default='power', choices=LEVELS, help='the same choice for the noise recordings')
     ap.add_argument('--seed', type=int, default=None, help='default: config.seed')
     ap.add_argument('--device', default='cuda:0')
     a = ap.parse_args(argv)
@@ -71,7 +78,7 @@ def main():
     store = MixingAudioStore.from_wav([os.path.join(a.clean_dir, f) for f in clean_names],
                                       [os.path.join(a.noise_dir, f) for f in noise_names], config, torch.device(a.device),
                                       ids=clean_names, noise_ids=noise_names, snr_db=a.snr_db or SNR_LEVELS_DB,
-                                      snr_range=a.snr_range)
+                                      snr_range=a.snr_range, level=a.level, noise_level=a.noise_level)
     fixed = store.materialise(generator=torch.Generator().manual_seed(int(config.seed if a.seed is None else a.seed)))
     draws = store.last_draws
     clean, noisy = fixed.clean.cpu().numpy(), fixed.noisy.cpu().numpy()

@@ -10,7 +10,8 @@
 The mode comes first, as in the reference's `train.py dcs 0`: the model code reads it from sys.argv[1].  Files are paired by
 name (mono 16-bit PCM at config.file_sr).  With --noise-dir instead of --noisy-dir there are no pairs: every training item is
 mixed on the device with a drawn noise recording, noise start and SNR (--snr-db levels, default 15,10,5,0, or --snr-range), by
-whole-recording mean powers; the validation files are mixed once, from a generator seeded by config.seed.  The train / validation split follows the reference's data.py: a seeded shuffle of
+whole-recording mean powers or, with --level p56 / --noise-level p56, by ITU-T P.56 active speech levels (measured once per store,
+on the device); the validation files are mixed once, from a generator seeded by config.seed.  The train / validation split follows the reference's data.py: a seeded shuffle of
 the sorted file names, --val-split percent (80) for training; it is written to OUT/partition.json and reused on resume.
 OUT receives last.ckpt after every epoch, best.ckpt when the monitored value improved, metrics.jsonl, and final.ckpt — the SWA
 weights, the file tools/enhance.py and tools/evaluate.py should load — after the last epoch."""
@@ -24,6 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'dcs-net_amd'))
 
 MODES = ('dcs', 'drs', 'dc', 'dr')
+LEVELS = ('power', 'p56')                                    # dcsnet.audio_store.LEVELS
 
 
 def partition(clean_dir, noisy_dir, out_dir, val_split, seed):
@@ -72,6 +74,12 @@ def parse_args(argv=None):
     ap.add_argument('--snr-db', type=_snr_levels, default=None, help='with --noise-dir: the SNR levels to draw from (15,10,5,0)')
     ap.add_argument('--snr-range', type=float, nargs=2, metavar=('LO', 'HI'), default=None,
                     help='with --noise-dir: a uniform SNR in [LO, HI] dB instead of levels')
+    ap.add_argument('--level', default='power', choices=LEVELS,
+                    help="with --noise-dir: what the SNR takes as the level of a clean recording: 'power', its whole-recording mean "
+                         "square, or 'p56', its ITU-T P.56 active speech level (pauses left out, as VoiceBank+DEMAND was mixed).  A "
+                         'property of the store, like --snr-db: a resumed run must be given the same value')
+    ap.add_argument('--noise-level', default='power', choices=LEVELS,
+                    help='with --noise-dir: the same choice for the noise recordings; a resumed run must be given the same value')
     ap.add_argument('--out', required=True, help='the run directory')
     ap.add_argument('--epochs', type=int, default=None, help='default: config.max_epochs')
     ap.add_argument('--batch', type=int, default=None, help='default: config.batch_size')
@@ -92,6 +100,8 @@ def parse_args(argv=None):
         ap.error('--snr-db and --snr-range exclude each other')
     if a.noise_dir is None and (a.snr_db is not None or a.snr_range is not None):
         ap.error('--snr-db / --snr-range need --noise-dir')
+    if a.noise_dir is None and (a.level != 'power' or a.noise_level != 'power'):
+        ap.error('--level / --noise-level need --noise-dir')
     if a.snr_range is not None and not a.snr_range[0] <= a.snr_range[1]:
         ap.error(f'--snr-range {a.snr_range[0]} {a.snr_range[1]}: LO must not exceed HI')
     if a.mode in ('drs', 'dr') and a.dtype == 'bf16':
@@ -131,7 +141,8 @@ def main():
         def mixing(k):
             return MixingAudioStore.from_wav([os.path.join(a.clean_dir, f) for f in part[k]],
                                              [os.path.join(a.noise_dir, f) for f in noise], config, dev, ids=part[k],
-                                             noise_ids=noise, snr_db=a.snr_db or SNR_LEVELS_DB, snr_range=a.snr_range)
+                                             noise_ids=noise, snr_db=a.snr_db or SNR_LEVELS_DB, snr_range=a.snr_range,
+                                             level=a.level, noise_level=a.noise_level)
         # validation is one fixed mixture per file, the same in every run and resume (its noise copy goes with the temporary);
         # training mixes afresh in every batch
         fixed = mixing('validation').materialise(generator=torch.Generator().manual_seed(int(config.seed)))
