@@ -90,6 +90,48 @@ class ComplexSpatialAttention(nn.Module):
         return nf.complex_sigmoid(self.conv1(torch.cat([mean_c, max_c], dim=1)))
 
 
+class ReplayDropout(nn.Module):
+    """Stands in for ``dropout_conv`` / ``dropout_fc`` of a C_NETWORK_Oracle: multiplies ``view_as_real(z)`` by the next
+    mask of ``masks`` (tensors of that shape holding 0 or 1 / (1 - p)), in call order — 7 encoder sites and 7 decoder
+    sites for ``dropout_conv``, 1 for ``dropout_fc``.  Raises on a shape mismatch and when it is called more often than
+    it has masks; ``finish()`` raises if masks are left over (``replay_dropout`` calls it after every forward pass).
+    Active in ``.eval()`` too: what it replays is the caller's business."""
+
+    def __init__(self, masks):
+        super().__init__()
+        self.masks = list(masks)
+        self.calls = 0
+
+    def forward(self, v):
+        if self.calls >= len(self.masks):
+            raise RuntimeError(f'ReplayDropout: call {self.calls + 1} but only {len(self.masks)} masks')
+        m = self.masks[self.calls]
+        if tuple(m.shape) != tuple(v.shape):
+            raise ValueError(f'ReplayDropout: mask {self.calls} has shape {tuple(m.shape)}, the site {tuple(v.shape)}')
+        self.calls += 1
+        return v * m.to(v.dtype)
+
+    def finish(self):
+        if self.calls != len(self.masks):
+            raise RuntimeError(f'ReplayDropout: {len(self.masks) - self.calls} of {len(self.masks)} masks left over')
+
+
+def replay_dropout(net, conv_masks, fc_masks):
+    """Put ReplayDropout modules in place of ``net.dropout_conv`` / ``net.dropout_fc`` for ONE forward pass: a forward hook
+    on ``net`` checks that both lists were used up.  Returns the two modules."""
+    net.dropout_conv, net.dropout_fc = ReplayDropout(conv_masks), ReplayDropout(fc_masks)
+    old = getattr(net, '_replay_hook', None)
+    if old is not None:
+        old.remove()
+
+    def done(mod, args, out):
+        mod.dropout_conv.finish()
+        mod.dropout_fc.finish()
+
+    net.__dict__['_replay_hook'] = net.register_forward_hook(done)
+    return net.dropout_conv, net.dropout_fc
+
+
 class C_NETWORK_Oracle(nn.Module):
     """c_network.py:88-226.  ``hp`` overrides HPARAMS (tests pass dropout 0)."""
 

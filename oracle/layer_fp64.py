@@ -362,17 +362,48 @@ def _act_with_decisions(z, act, decided, thr=TIE):
     return torch.complex(f(z.real, decided.real), f(z.imag, decided.imag)), count
 
 
-def block_reference(x, g_out, wide, bn=None, act='none', attention=None, drop_last=0, decided=None, max_choice=None):
+class _KeepFn(torch.autograd.Function):
+    """v * keep_fwd forward, g * keep_bwd backward: a dropout whose backward regenerates its mask (comparator tests hand in
+    two different ones: a backward that lost its scale or its seed offset)."""
+
+    @staticmethod
+    def forward(ctx, v, keep_fwd, keep_bwd):
+        ctx.save_for_backward(keep_bwd)
+        return v * keep_fwd
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.saved_tensors[0], None, None
+
+
+def _apply_keep(a, keep, rd):
+    """Complex a [B,C,H,W] times the real mask keep [B,C,H,W,2] (or the pair (forward mask, backward mask))."""
+    fwd, bwd = keep if isinstance(keep, (tuple, list)) else (keep, None)
+    v = torch.view_as_real(a)
+    if tuple(fwd.shape) != tuple(v.shape):
+        raise ValueError(f'block_reference: keep has shape {tuple(fwd.shape)}, the output {tuple(v.shape)}')
+    v = v * fwd.to(rd) if bwd is None else _KeepFn.apply(v, fwd.to(rd), bwd.to(rd))
+    return torch.view_as_complex(v)
+
+
+def block_reference(x, g_out, wide, bn=None, act='none', attention=None, drop_last=0, decided=None, max_choice=None, keep=None,
+                    keep_before_attention=False):
     """One CBN (training mode, fresh running statistics) and / or one attention block on complex64 input x with cotangent
     g_out, in fp64 (wide) or fp32, differentiated by autograd.  bn = (weight [C,3], bias [C,2]); attention = the six
     parameters in ATT_NAMES order.  Returns dict(y, gx[, running_mean, running_covar, g_weight, g_bias][, g_att: list]).
 
     decided: see _act_with_decisions; max_choice: see _spatial_with_choice.  drop_last = n > 0 (CBN only, comparator tests): the gradients a backward gives whose reduction sums leave out the LAST n
     pixels — every sum over pixels (the two that couple g_x to the batch statistics, and with them the parameter
-    gradients) is taken over the cotangent with those pixels zeroed, the per-pixel term keeps the whole cotangent."""
+    gradients) is taken over the cotangent with those pixels zeroed, the per-pixel term keeps the whole cotangent.
+
+    keep: a dropout mask [B,C,H,W,2] of 0 and 1 / (1 - p) (oracle/dropout_mask.keep_nchw) multiplied into the block's output
+    where the kernels drop — after the activation of a CBN-only block (cbn_apply_kernel), after the spatial-attention multiply
+    of a block with attention (attention_apply_kernel); `y` is the dropped output.  Comparator tests only: keep = (forward
+    mask, backward mask), and keep_before_attention = True (the mask between the activation and the attention)."""
     cd, rd = (torch.complex128, torch.float64) if wide else (torch.complex64, torch.float32)
     C = x.shape[1]
     out = {}
+    drop_mask = keep                                 # (`keep` below is drop_last's pixel selection)
     with cdtype(cd):
         mod = None
         if bn is not None:
@@ -401,10 +432,14 @@ def block_reference(x, g_out, wide, bn=None, act='none', attention=None, drop_la
                     a = _POST[act](mod(a))
                 else:
                     a, out['undecided_activations'] = _act_with_decisions(mod(a), act, decided)
+            if drop_mask is not None and keep_before_attention:
+                a = _apply_keep(a, drop_mask, rd)
             if ca is not None:
                 z = ca(a) * a
                 a = (sa(z) if not max_choice else _spatial_with_choice(sa, z, max_choice)) * z
                 out['z'] = z.detach()                # what the spatial attention takes its channel maximum of
+            if drop_mask is not None and not keep_before_attention:
+                a = _apply_keep(a, drop_mask, rd)
             (torch.view_as_real(a) * torch.view_as_real(g.to(cd))).sum().backward()
             return a.detach(), torch.complex(xr.grad, xi.grad)
 

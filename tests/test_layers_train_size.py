@@ -321,12 +321,12 @@ def dev():
     torch.set_num_threads(threads)
 
 
-def _record(path, value):
+def _record(path, value, name='layer_parity.json'):
     """Figures -> $DCS_PARITY_DIR/layer_parity.json, default parity_out/ in the repository (a full run's file is committed as
     profiles/layer_parity.json): path = nested keys.  (The directory the two older _record helpers write to is named after
-    one particular job runner; this record goes where its caller says.)"""
+    one particular job runner; this record goes where its caller says.)  name: another module's file in the same directory."""
     out = os.path.join(os.environ.get('DCS_PARITY_DIR') or
-                       os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'parity_out'), 'layer_parity.json')
+                       os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'parity_out'), name)
     try:
         os.makedirs(os.path.dirname(out), exist_ok=True)
         d = json.load(open(out)) if os.path.exists(out) else {}
