@@ -11,7 +11,7 @@
 //                                  thread t adds samples t, t + 256, ... in ascending order, then ragged_common.h's block_sum
 //                                  (a fixed tree): the same bits on every run; 0 for an empty recording
 //   audio_mix_ragged_kernel      whole-recording mixtures for a materialised set: one thread per sample of the flat clean
-//                                  store; it finds its item by bisection of the offsets (as resample_sinc_kernel does); an item
+//                                  store; it finds its item by owner() of the offsets (as resample_sinc_kernel does); an item
 //                                  whose draw cannot be followed gets noisy = clean
 //   audio_mix_stft_batch_kernel  audio_stft_batch_kernel (audio_store.hip) with the noisy sample replaced by the mixture rule at
 //                                  q = start_b + reflect_index(...): grid, LDS, the order clean -> noise -> noisy and the bin
@@ -96,11 +96,7 @@ __global__ __launch_bounds__(256) void audio_mix_ragged_kernel(const float* __re
                                                                const float* __restrict__ gain, float* __restrict__ noisy) {
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     if (g >= total) return;
-    int lo = 0, hi = n_items;                                // off[lo] <= g < off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= g) lo = mid; else hi = mid;
-    }
+    const int lo = dcs_ragged::owner(off, n_items, g);       // off[0] <= g is the caller's invariant; q >= 0 is tested below
     const float c = clean[g];
     const long q = g - off[lo];
     const NoiseDraw d = noise_draw(noise, noff, n_noise, noise_idx[lo], noise_start[lo], gain[lo]);

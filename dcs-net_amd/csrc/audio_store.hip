@@ -9,7 +9,7 @@
 //                               transpose / reshape of _apply_sinc_resample_kernel.  The taps h float[n][K] are computed on the
 //                               host in fp64 and rounded once (ops.sinc_resample_taps).  One thread per output sample, fp32
 //                               accumulation in tap order: the result does not depend on the launch geometry.  Rows are ragged
-//                               (x_off / y_off, int64 prefix offsets); a thread finds its row by bisection of y_off.
+//                               (x_off / y_off, int64 prefix offsets); a thread finds its row by owner() of y_off.
 //   audio_stft_batch_kernel   one training batch from the resident 16 kHz store in one launch: per item b the crop
 //                               [start_b, start_b + L) of utterance idx_b (zero past its end: data.py:90-104), the reflect padding
 //                               of torch.stft(center=True), the windowed frames of clean, noise = noisy - clean (time domain,
@@ -25,6 +25,7 @@
 // captured graph replays with what the host wrote there since); an index outside [0, n_items) or a start whose crop would leave
 // the utterance yields zeros for that item, so no value in those buffers makes the kernel read outside the store.
 #include "audio_batch_common.h"
+#include "ragged_common.h"
 
 namespace {
 
@@ -37,11 +38,7 @@ __global__ __launch_bounds__(256) void resample_sinc_kernel(const float* __restr
                                                             int width) {
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     if (g >= total) return;
-    int lo = 0, hi = rows;                                   // y_off[lo] <= g < y_off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (y_off[mid] <= g) lo = mid; else hi = mid;
-    }
+    const int lo = dcs_ragged::owner(y_off, rows, g);
     const long xb = x_off[lo], L = x_off[lo + 1] - xb;
     const long m = g - y_off[lo], j = m / n;
     const int i = (int)(m - j * n);

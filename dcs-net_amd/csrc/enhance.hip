@@ -18,12 +18,13 @@
 //                                  leaving [0, Tp_i) yields zeros and reads nothing: the last batch is padded with such rows,
 //                                  and no value in the table makes the kernel read outside the store.
 //   segments_stitch_kernel       segment waveforms [rows][hop (T - 1)] -> one ragged row per recording (len_i samples, the
-//                                  store's offsets).  One thread per output sample finds its recording by bisection of the
-//                                  offsets (resample_sinc_kernel's), then its segment; inside an overlap of n samples, sample j
+//                                  store's offsets).  One thread per output sample finds its recording by owner() of the
+//                                  offsets (ragged_common.h), then its segment; inside an overlap of n samples, sample j
 //                                  is a + w (b - a), w = (j + 0.5) / n, a the earlier and b the later segment's sample;
 //                                  everywhere else the one covering segment's sample is copied unchanged.  Plain stores, no
 //                                  atomics: bit-reproducible.  Optionally the same thread writes the sample as 16-bit PCM.
 #include "fft512_common.h"
+#include "ragged_common.h"
 
 #ifndef DCS_AUDIO_FRAMES_PER_WG
 #define DCS_AUDIO_FRAMES_PER_WG 8
@@ -117,11 +118,7 @@ __global__ __launch_bounds__(256) void segments_stitch_kernel(const float* __res
                                                               long stride, int ov) {
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     if (g >= total) return;
-    int lo = 0, hi = recs;                                   // y_off[lo] <= g < y_off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (y_off[mid] <= g) lo = mid; else hi = mid;
-    }
+    const int lo = dcs_ragged::owner(y_off, recs, g);
     const long m = g - y_off[lo];
     const long r0 = seg_first[lo], nseg = seg_first[lo + 1] - r0;
     long s = m / stride;

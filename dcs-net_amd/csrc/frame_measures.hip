@@ -3,14 +3,12 @@
 // ragged convention (ragged_common.h: one flat float buffer + int64 offsets[n + 1] on the device).  The host function
 // dcsnet/metrics.py::frame_measures is the numerics contract; everything here is fp64 until the three float32 outputs.
 //
-// Framing at rate fs: N = round(0.03 fs) samples, hop S = N / 4, F = (L - N) / S frames for L >= N + S (else 0), frame k at
-// k S, window double[N] from the host (metrics._measure_window: the same bits as the host function's).  LPC order P = 16 for
-// fs >= 10000, else 10.
+// Framing, workspace (3 value planes) and the prefix launch are ragged_frames.h's; the window double[N] comes from the host
+// (metrics._measure_window: the same bits as the host function's).  LPC order P = 16 for fs >= 10000, else 10.  This source
+// owns the LPC recursion, the cepstrum and the Toeplitz forms, and:
 //
-//   ragged_prefix_kernel<PrefixMeasureFrames>   one workgroup: fbase[i] = the frames of the recordings before i, clamped to
-//                                                 Fcap = total / S >= the frames of all recordings together
 //   frame_measures_kernel<P>                    one wave64 per frame slot g < fbase[n] (grid Fcap, from the host integer
-//                                                 total; the workgroup finds its recording by bisection of fbase): both windowed
+//                                                 total; frame_slot finds its samples): both windowed
 //                                                 frames into LDS (2 N doubles), the two energies and the 2 (P + 1)
 //                                                 autocorrelation lags with the samples split over the 64 lanes (lane t adds
 //                                                 t, t + 64, ... in ascending order, then a fixed butterfly), the two
@@ -18,56 +16,23 @@
 //                                                 the two quadratic forms on lane 0 -> vals[0..2][g] = the frame's segmental
 //                                                 SNR (clamped to [-10, 35] dB), LLR (clamped to [0, 2]), CD (clamped to
 //                                                 [0, 10]); valid[g] = both recursions kept R[0] > 0 and every E_i > 0
-//   recording_measures_kernel                   one workgroup per recording, any number of frames: the SSNR mean; for LLR and
-//                                                 CD the K-th smallest valid value t (K = max(1, floor(0.95 V + 0.5)), V valid
-//                                                 frames) by binary radix selection on the bit patterns (non-negative doubles:
-//                                                 bit order = numeric order; one pass per bit, both measures in one pass,
-//                                                 counts by a fixed integer reduction), then (sum of the v < t + (K - #{v < t})
-//                                                 t) / K, the sum over the frame slots in a fixed order: no sort, ties handled
+//   recording_measures_kernel                   one workgroup per recording, any number of frames: the SSNR mean over all F
+//                                                 frames; for LLR and CD the mean of the K smallest valid values
+//                                                 (K = max(1, floor(0.95 V + 0.5)), V valid frames) by trimmed_means<2, true>;
+//                                                 NaN for all three without a frame, for LLR and CD without a valid one
 //
-// Workspace: frame base long[n + 1] | vals double[3][Fcap] | valid int[Fcap]: it follows the total length.
 // Three launches whatever n is (two when total < S).  No atomics, no cross-workgroup synchronisation, no host read-back:
 // capturable, bit-reproducible, and a recording's scores do not depend on its neighbours.
-#include "ragged_common.h"
+#include "ragged_frames.h"
 
 namespace {
 
 using namespace dcs_ragged;
 
-constexpr int kMinRate = 8000, kMaxRate = 48000;
 constexpr int kMaxOrder = 16;
 constexpr double kEps = 2.220446049250313e-16;                // np.finfo(np.float64).eps
-constexpr unsigned long long kMagnitude = 0x7fffffffffffffffull;
 
-struct Geometry {
-    int N, S, P;
-};
-inline Geometry geometry(int fs) {
-    Geometry g;
-    g.N = (3 * fs + 50) / 100;                                // round(0.03 fs)
-    g.S = g.N / 4;
-    g.P = fs >= 10000 ? 16 : 10;
-    return g;
-}
-inline bool bad_rate(int fs) { return fs < kMinRate || fs > kMaxRate; }
-inline long align256(long n) { return (n + 255) & ~255L; }
-
-struct PrefixMeasureFrames {                                  // v = (L - N) / S for L >= N + S
-    long N, S;
-    __device__ __forceinline__ long operator()(long L) const { return L >= N + S ? (L - N) / S : 0; }
-};
-
-struct Layout {
-    long Fcap, off_vals, off_valid, bytes;
-};
-inline Layout layout(long n, long total, const Geometry& g) {
-    Layout s;
-    s.Fcap = total / g.S;
-    s.off_vals = align256((n + 1) * (long)sizeof(long));
-    s.off_valid = s.off_vals + align256(3 * s.Fcap * (long)sizeof(double));
-    s.bytes = s.off_valid + align256(s.Fcap * (long)sizeof(int));
-    return s;
-}
+inline int lpc_order(int fs) { return fs >= 10000 ? kMaxOrder : 10; }
 
 // the published lpcoeff on R[0 .. P]: A[0 .. P] = [1, -a], c[1 .. P] the LPC cepstrum of A; returns R[0] > 0 and every E_i > 0
 template <int P>
@@ -127,8 +92,6 @@ __device__ __forceinline__ double toeplitz_form(const double* __restrict__ A, co
     return q;
 }
 
-__device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // dynamic LDS: double[2 N], the windowed clean frame and the windowed estimate
 template <int P>
 __global__ __launch_bounds__(64) void frame_measures_kernel(const float* __restrict__ clean, const float* __restrict__ est,
@@ -140,16 +103,8 @@ __global__ __launch_bounds__(64) void frame_measures_kernel(const float* __restr
     __shared__ double R[2][P + 1], A[2][P + 1], C[2][P + 1];
     __shared__ int ok[2];
     const long g = blockIdx.x;
-    if (g >= fbase[n]) return;                               // uniform over the workgroup; fbase[n] <= Fcap
-    int lo = 0, hi = n;                                      // fbase[lo] <= g < fbase[hi]: the LAST recording that starts at or before g
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (fbase[mid] <= g) lo = mid; else hi = mid;
-    }
-    long first;
-    rec_span(offsets, lo, total, &first);
-    // frame k = g - fbase[lo] < fbase[lo + 1] - fbase[lo] <= (L - N) / S: its samples end before the recording's
-    const long base = first + (g - fbase[lo]) * S;
+    long base;
+    if (!frame_slot(offsets, n, total, fbase, g, S, &base)) return;
     const float* __restrict__ c = clean + base;
     const float* __restrict__ e = est + base;
     double* fx = frames;
@@ -204,20 +159,6 @@ __global__ __launch_bounds__(64) void frame_measures_kernel(const float* __restr
     }
 }
 
-// every thread of a 256-thread workgroup returns the sum of v over it (integers; red: LDS [4])
-__device__ __forceinline__ unsigned long long block_sum_ull(unsigned long long v, unsigned long long* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();                                         // red may still be read from the previous sum
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ __forceinline__ unsigned long long magnitude_bits(double v) {
-    return (unsigned long long)__double_as_longlong(v) & kMagnitude;       // -0.0 orders as 0.0
-}
-
 __global__ __launch_bounds__(256) void recording_measures_kernel(const long* __restrict__ fbase, long Fcap,
                                                                  const double* __restrict__ vals, const int* __restrict__ valid,
                                                                  float* __restrict__ out_ssnr, float* __restrict__ out_llr,
@@ -237,8 +178,6 @@ __global__ __launch_bounds__(256) void recording_measures_kernel(const long* __r
         return;
     }
     const double* __restrict__ snr = vals + fb;
-    const double* __restrict__ llr = vals + Fcap + fb;
-    const double* __restrict__ cd = vals + 2 * Fcap + fb;
     const int* __restrict__ ok = valid + fb;
     double s = 0.0;
     unsigned long long cnt = 0;
@@ -257,92 +196,41 @@ __global__ __launch_bounds__(256) void recording_measures_kernel(const long* __r
         return;
     }
     const long K0 = (19 * V + 10) / 20;                      // floor(0.95 V + 0.5), exactly
-    const long K = K0 > 1 ? K0 : 1;
-    // the K-th smallest valid value of each measure, one bit per pass from the top: among the values that share the bits
-    // found so far, count those whose next bit is 0 (LLR's count in the low word, CD's in the high word: F < 2^31)
-    unsigned long long pl = 0, pc = 0;
-    long kl = K, kc = K;
-    for (int bit = 62; bit >= 0; --bit) {
-        unsigned long long c0 = 0;
-        for (long i = t; i < F; i += 256) {
-            if (!ok[i]) continue;
-            const unsigned long long ul = magnitude_bits(llr[i]), uc = magnitude_bits(cd[i]);
-            if ((ul >> bit) == (pl >> bit)) c0 += 1ull;      // the bits above `bit` agree and bit `bit` is 0 (pl's still is)
-            if ((uc >> bit) == (pc >> bit)) c0 += 1ull << 32;
-        }
-        c0 = block_sum_ull(c0, red4);
-        const long zl = (long)(c0 & 0xffffffffull), zc = (long)(c0 >> 32);
-        if (kl > zl) {
-            kl -= zl;
-            pl |= 1ull << bit;
-        }
-        if (kc > zc) {
-            kc -= zc;
-            pc |= 1ull << bit;
-        }
-    }
-    double sl = 0.0, sc = 0.0;
-    unsigned long long below = 0;
-    for (long i = t; i < F; i += 256) {
-        if (!ok[i]) continue;
-        const double vl = llr[i], vc = cd[i];
-        if (magnitude_bits(vl) < pl) {
-            sl += vl;
-            below += 1ull;
-        }
-        if (magnitude_bits(vc) < pc) {
-            sc += vc;
-            below += 1ull << 32;
-        }
-    }
-    sl = block_sum(sl, red);
-    sc = block_sum(sc, red);
-    below = block_sum_ull(below, red4);
+    double mean[2];                                          // of the K smallest valid LLR (plane 1) and CD (plane 2) values
+    trimmed_means<2, true>(vals + Fcap + fb, Fcap, ok, F, K0 > 1 ? K0 : 1, red, red4, mean);
     if (t == 0) {
-        const double tl = __longlong_as_double((long long)pl), tc = __longlong_as_double((long long)pc);
-        out_llr[b] = (float)((sl + (double)(K - (long)(below & 0xffffffffull)) * tl) / (double)K);
-        out_cd[b] = (float)((sc + (double)(K - (long)(below >> 32)) * tc) / (double)K);
+        out_llr[b] = (float)mean[0];
+        out_cd[b] = (float)mean[1];
     }
 }
 
 }  // namespace
 
 extern "C" long dcs_frame_measures_ragged_workspace_bytes(int n, long total, int fs) {
-    if (n <= 0 || n > kMaxRecordings || total < 0 || total > kMaxTotal || bad_rate(fs)) return DCS_ERR_BADARG;
-    const Layout s = layout(n, total, geometry(fs));
-    if (s.Fcap > 0x7fffffffL) return DCS_ERR_BADARG;          // one workgroup per frame slot
-    return s.bytes;
+    return frame_workspace_bytes(n, total, fs, 3);
 }
 
 extern "C" int dcs_frame_measures_ragged_f32(const float* clean, const float* est, const long* offsets, int n, long total, int fs,
                                              const double* window, int window_len, float* out_ssnr, float* out_llr, float* out_cd,
                                              void* workspace, long workspace_bytes, dcs_stream_t stream) {
-    if (bad_ragged(offsets, n, total) || bad_rate(fs) || !window || !out_ssnr || !out_llr || !out_cd || !workspace ||
-        (total > 0 && (!clean || !est)))
-        return DCS_ERR_BADARG;
-    const Geometry g = geometry(fs);
-    const Layout s = layout(n, total, g);
-    if (window_len != g.N || s.Fcap > 0x7fffffffL) return DCS_ERR_BADARG;
-    if (workspace_bytes < s.bytes) return DCS_ERR_WORKSPACE;
-    char* ws = static_cast<char*>(workspace);
-    long* fbase = reinterpret_cast<long*>(ws);
-    double* vals = reinterpret_cast<double*>(ws + s.off_vals);
-    int* valid = reinterpret_cast<int*>(ws + s.off_valid);
-    hipStream_t st = dcs_stream(stream);
-    DCS_LAUNCH(ragged_prefix_kernel<PrefixMeasureFrames>, dim3(1), dim3(256), 0, st, offsets, n, total,
-               PrefixMeasureFrames{g.N, g.S}, s.Fcap, fbase);
-    DCS_CHECK_LAUNCH();
+    if (!out_ssnr || !out_llr || !out_cd) return DCS_ERR_BADARG;
+    FrameGeometry g;
+    FrameLayout s;
+    hipStream_t st;
+    const int rc = frame_slots_begin(clean, est, offsets, n, total, fs, window, window_len, 3, workspace, workspace_bytes, stream,
+                                     &g, &s, &st);
+    if (rc != DCS_OK) return rc;
     if (s.Fcap > 0) {
         const size_t lds = 2 * (size_t)g.N * sizeof(double);
-        if (g.P == kMaxOrder)
-            DCS_LAUNCH(frame_measures_kernel<16>, dim3((unsigned)s.Fcap), dim3(64), lds, st, clean, est, offsets, n, total, fbase,
-                       window, g.N, g.S, s.Fcap, vals, valid);
+        if (lpc_order(fs) == kMaxOrder)
+            DCS_LAUNCH(frame_measures_kernel<16>, dim3((unsigned)s.Fcap), dim3(64), lds, st, clean, est, offsets, n, total, s.fbase,
+                       window, g.N, g.S, s.Fcap, s.vals, s.valid);
         else
-            DCS_LAUNCH(frame_measures_kernel<10>, dim3((unsigned)s.Fcap), dim3(64), lds, st, clean, est, offsets, n, total, fbase,
-                       window, g.N, g.S, s.Fcap, vals, valid);
+            DCS_LAUNCH(frame_measures_kernel<10>, dim3((unsigned)s.Fcap), dim3(64), lds, st, clean, est, offsets, n, total, s.fbase,
+                       window, g.N, g.S, s.Fcap, s.vals, s.valid);
         DCS_CHECK_LAUNCH();
     }
-    DCS_LAUNCH(recording_measures_kernel, dim3(n), dim3(256), 0, st, fbase, s.Fcap, vals, valid, out_ssnr, out_llr, out_cd);
+    DCS_LAUNCH(recording_measures_kernel, dim3(n), dim3(256), 0, st, s.fbase, s.Fcap, s.vals, s.valid, out_ssnr, out_llr, out_cd);
     DCS_CHECK_LAUNCH();
     return DCS_OK;
 }

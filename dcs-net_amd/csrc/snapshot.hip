@@ -6,7 +6,7 @@
 //
 // The item table and the cumulative workgroup table are DEVICE memory: the host entry point reads neither.  What can only be
 // known from the table is checked where it is read: an item that breaks a rule of include/dcsnet_hip.h is not copied at all.
-#include "dcs_common.h"
+#include "ragged_common.h"                                   // owner(): which item a block of the cumulative table belongs to
 
 namespace {
 constexpr int kThreads = 256;
@@ -33,11 +33,7 @@ __global__ __launch_bounds__(kThreads) void snapshot_kernel(const dcs_snapshot_i
             if (!item_ok(items[i], dst_words)) nonfinite[i] = -1;
     const long total = first_block[n];
     for (long vb = blockIdx.x; vb < total; vb += gridDim.x) {          // (uniform over the workgroup)
-        int lo = 0, hi = n;                                      // first_block[lo] <= vb < first_block[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (first_block[mid] <= vb) lo = mid; else hi = mid;
-        }
+        const int lo = dcs_ragged::owner(first_block, n, vb);
         const dcs_snapshot_item it = items[lo];
         const long w0 = (vb - first_block[lo]) * kBlockWords + 4 * (long)threadIdx.x;
         // a table whose block counts disagree with its items leaves words uncopied; it cannot make an access leave src or dst

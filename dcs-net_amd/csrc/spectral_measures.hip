@@ -2,12 +2,12 @@
 // of whole recordings of different lengths, for the project's ragged convention (ragged_common.h).  The host function
 // dcsnet/metrics.py::spectral_measures is the numerics contract; everything here is fp64 until the two float32 outputs.
 //
-// Framing as in frame_measures.hip: N = round(0.03 fs), hop S = N / 4, F = (L - N) / S frames for L >= N + S (else 0), window
-// double[N] from the host.  nfft = 2^LOG = the smallest power of two >= 2 N (LOG = 9 .. 12), H = nfft / 2 bins.  25 critical bands
-// as a compact table from the host (metrics.compact_bank: first bin, offset into the weights, the weights' own bits).
+// Framing, workspace (2 value planes) and the prefix launch are ragged_frames.h's, shared with frame_measures.hip; the window
+// double[N] comes from the host.  nfft = 2^LOG = the smallest power of two >= 2 N (LOG = 9 .. 12), H = nfft / 2 bins.  25 critical
+// bands as a compact table from the host (metrics.compact_bank: first bin, offset into the weights, the weights' own bits).
+// This source owns the Stockham passes, the band sums and the peak search, and:
 //
-//   ragged_prefix_kernel<PrefixSpectralFrames>  one workgroup: fbase[i] = the frames of the recordings before i, clamped to Fcap
-//   spectral_frame_kernel<LOG>                  one workgroup of 256 per frame slot g < fbase[n] (bisection of fbase):
+//   spectral_frame_kernel<LOG>                  one workgroup of 256 per frame slot g < fbase[n] (frame_slot finds its samples):
 //       z = x w + i y w, zero-padded, into LDS (double2[nfft], the kernel's only LDS: 8 KiB .. 64 KiB);
 //       one complex Stockham transform in that buffer: a radix-2 pass when LOG is odd, then radix-4 passes; every thread reads
 //       the inputs of its butterflies into registers, the workgroup synchronises, and it writes their outputs (autosort, no
@@ -25,54 +25,26 @@
 //       the grid is the capacity Fcap = total / S, not the frame count (the host does not read the offsets): per recording
 //       about N / S = 4 slots, and all L / S of one shorter than N + S, go to workgroups that exit at once
 //   spectral_recording_kernel                   one workgroup per recording: the mean of the valid fwSegSNR values; the WSS
-//       trimmed mean over ALL F frames (K = max(1, floor(0.95 F + 0.5))) by the binary radix selection of frame_measures.hip
-//       (WSS values are non-negative doubles: bit order = numeric order): no sort, ties handled
+//       trimmed mean over ALL F frames (K = max(1, floor(0.95 F + 0.5))) by trimmed_means<1, false> (WSS values are
+//       non-negative doubles); NaN for both without a frame, for fwSegSNR without a valid one
 //
-// Workspace: frame base long[n + 1] | vals double[2][Fcap] | valid int[Fcap], Fcap = total / S.
 // Three launches whatever n is (two when total < S).  No atomics, no cross-workgroup synchronisation, no host read-back:
 // capturable, bit-reproducible, and a recording's scores do not depend on its neighbours.
-#include "ragged_common.h"
+#include "ragged_frames.h"
 
 namespace {
 
 using namespace dcs_ragged;
 
-constexpr int kMinRate = 8000, kMaxRate = 48000;
 constexpr int kBands = 25;
 constexpr int kThreads = 256;
 constexpr double kEps = 2.220446049250313e-16;                // np.finfo(np.float64).eps
 constexpr double kFloor = 1e-10;                              // of a band's power, before the logarithm
-constexpr unsigned long long kMagnitude = 0x7fffffffffffffffull;
 
-struct Geometry {
-    int N, S, log_nfft;
-};
-inline Geometry geometry(int fs) {
-    Geometry g;
-    g.N = (3 * fs + 50) / 100;                                // round(0.03 fs)
-    g.S = g.N / 4;
-    g.log_nfft = 9;
-    while ((1 << g.log_nfft) < 2 * g.N) ++g.log_nfft;         // fs <= 48000: N <= 1440, nfft <= 4096
-    return g;
-}
-inline bool bad_rate(int fs) { return fs < kMinRate || fs > kMaxRate; }
-inline long align256(long n) { return (n + 255) & ~255L; }
-
-struct PrefixSpectralFrames {                                 // v = (L - N) / S for L >= N + S
-    long N, S;
-    __device__ __forceinline__ long operator()(long L) const { return L >= N + S ? (L - N) / S : 0; }
-};
-
-struct Layout {
-    long Fcap, off_vals, off_valid, bytes;
-};
-inline Layout layout(long n, long total, const Geometry& g) {
-    Layout s;
-    s.Fcap = total / g.S;
-    s.off_vals = align256((n + 1) * (long)sizeof(long));
-    s.off_valid = s.off_vals + align256(2 * s.Fcap * (long)sizeof(double));
-    s.bytes = s.off_valid + align256(s.Fcap * (long)sizeof(int));
-    return s;
+inline int log_nfft(int N) {                                  // fs <= 48000: N <= 1440, nfft <= 4096
+    int log = 9;
+    while ((1 << log) < 2 * N) ++log;
+    return log;
 }
 
 __device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
@@ -80,7 +52,6 @@ __device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_doub
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
     return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
-__device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One Stockham pass of radix R (2 or 4) over buf[2^LOG] with Ns = the product of the radices before it: butterfly j < 2^LOG / R
 // takes buf[j + r 2^LOG / R] times w^(k r), k = j mod Ns, w = exp(-2 pi i / (Ns R)), and leaves its outputs at
@@ -146,16 +117,8 @@ __global__ __launch_bounds__(kThreads) void spectral_frame_kernel(
     constexpr int NFFT = 1 << LOG, H = NFFT / 2;
     extern __shared__ double2 buf[];
     const long g = blockIdx.x;
-    if (g >= fbase[n]) return;                               // uniform over the workgroup; fbase[n] <= Fcap
-    int lo = 0, hi = n;                                      // fbase[lo] <= g < fbase[hi]: the LAST recording that starts at or before g
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (fbase[mid] <= g) lo = mid; else hi = mid;
-    }
-    long first;
-    rec_span(offsets, lo, total, &first);
-    // frame k = g - fbase[lo] < fbase[lo + 1] - fbase[lo] <= (L - N) / S: its samples end before the recording's
-    const long base = first + (g - fbase[lo]) * S;
+    long base;
+    if (!frame_slot(offsets, n, total, fbase, g, S, &base)) return;
     const float* __restrict__ c = clean + base;
     const float* __restrict__ e = est + base;
     const int t = threadIdx.x;
@@ -278,20 +241,6 @@ __global__ __launch_bounds__(kThreads) void spectral_frame_kernel(
     }
 }
 
-// every thread of a 256-thread workgroup returns the sum of v over it (integers; red: LDS [4])
-__device__ __forceinline__ unsigned long long block_sum_ull(unsigned long long v, unsigned long long* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();                                         // red may still be read from the previous sum
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ __forceinline__ unsigned long long magnitude_bits(double v) {
-    return (unsigned long long)__double_as_longlong(v) & kMagnitude;       // -0.0 orders as 0.0
-}
-
 __global__ __launch_bounds__(256) void spectral_recording_kernel(const long* __restrict__ fbase, long Fcap,
                                                                  const double* __restrict__ vals, const int* __restrict__ valid,
                                                                  float* __restrict__ out_wss, float* __restrict__ out_fwssnr) {
@@ -308,7 +257,6 @@ __global__ __launch_bounds__(256) void spectral_recording_kernel(const long* __r
         }
         return;
     }
-    const double* __restrict__ wss = vals + fb;
     const double* __restrict__ fw = vals + Fcap + fb;
     const int* __restrict__ ok = valid + fb;
     double s = 0.0;
@@ -322,51 +270,24 @@ __global__ __launch_bounds__(256) void spectral_recording_kernel(const long* __r
     const long V = (long)block_sum_ull(cnt, red4);
     if (t == 0) out_fwssnr[b] = V > 0 ? (float)(s / (double)V) : nan;
     const long K0 = (19 * F + 10) / 20;                      // floor(0.95 F + 0.5), exactly
-    const long K = K0 > 1 ? K0 : 1;
-    // the K-th smallest WSS value, one bit per pass from the top: among the values that share the bits found so far, count
-    // those whose next bit is 0
-    unsigned long long p = 0;
-    long k = K;
-    for (int bit = 62; bit >= 0; --bit) {
-        unsigned long long c0 = 0;
-        for (long i = t; i < F; i += 256)
-            if ((magnitude_bits(wss[i]) >> bit) == (p >> bit)) c0 += 1;     // the bits above `bit` agree and bit `bit` is 0
-        const long z = (long)block_sum_ull(c0, red4);
-        if (k > z) {
-            k -= z;
-            p |= 1ull << bit;
-        }
-    }
-    double sb = 0.0;
-    unsigned long long below = 0;
-    for (long i = t; i < F; i += 256) {
-        const double v = wss[i];
-        if (magnitude_bits(v) < p) {
-            sb += v;
-            below += 1;
-        }
-    }
-    sb = block_sum(sb, red);
-    below = block_sum_ull(below, red4);
-    if (t == 0) out_wss[b] = (float)((sb + (double)(K - (long)below) * __longlong_as_double((long long)p)) / (double)K);
+    double mean[1];                                          // of the K smallest WSS values (plane 0), valid or not
+    trimmed_means<1, false>(vals + fb, Fcap, nullptr, F, K0 > 1 ? K0 : 1, red, red4, mean);
+    if (t == 0) out_wss[b] = (float)mean[0];
 }
 
 template <int LOG>
-void launch_frames(const Layout& s, hipStream_t st, const float* clean, const float* est, const long* offsets, int n, long total,
-                   const long* fbase, const double* window, const Geometry& g, const int* band_first, const int* band_offset,
-                   const double* band_weights, int n_weights, const double* twiddles, double* vals, int* valid) {
+void launch_frames(const FrameLayout& s, hipStream_t st, const float* clean, const float* est, const long* offsets, int n, long total,
+                   const double* window, const FrameGeometry& g, const int* band_first, const int* band_offset,
+                   const double* band_weights, int n_weights, const double* twiddles) {
     DCS_LAUNCH(spectral_frame_kernel<LOG>, dim3((unsigned)s.Fcap), dim3(kThreads), sizeof(double2) << LOG, st, clean, est, offsets,
-               n, total, fbase, window, g.N, g.S, band_first, band_offset, band_weights, n_weights,
-               reinterpret_cast<const double2*>(twiddles), s.Fcap, vals, valid);
+               n, total, s.fbase, window, g.N, g.S, band_first, band_offset, band_weights, n_weights,
+               reinterpret_cast<const double2*>(twiddles), s.Fcap, s.vals, s.valid);
 }
 
 }  // namespace
 
 extern "C" long dcs_spectral_measures_ragged_workspace_bytes(int n, long total, int fs) {
-    if (n <= 0 || n > kMaxRecordings || total < 0 || total > kMaxTotal || bad_rate(fs)) return DCS_ERR_BADARG;
-    const Layout s = layout(n, total, geometry(fs));
-    if (s.Fcap > 0x7fffffffL) return DCS_ERR_BADARG;          // one workgroup per frame slot
-    return s.bytes;
+    return frame_workspace_bytes(n, total, fs, 2);
 }
 
 extern "C" int dcs_spectral_measures_ragged_f32(const float* clean, const float* est, const long* offsets, int n, long total, int fs,
@@ -374,36 +295,29 @@ extern "C" int dcs_spectral_measures_ragged_f32(const float* clean, const float*
                                                 const int* band_offset, const double* band_weights, int band_weights_len,
                                                 const double* twiddles, int twiddles_len, float* out_wss, float* out_fwssnr,
                                                 void* workspace, long workspace_bytes, dcs_stream_t stream) {
-    if (bad_ragged(offsets, n, total) || bad_rate(fs) || !window || !band_first || !band_offset || !band_weights || !twiddles ||
-        !out_wss || !out_fwssnr || !workspace || (total > 0 && (!clean || !est)))
-        return DCS_ERR_BADARG;
-    const Geometry g = geometry(fs);
-    const Layout s = layout(n, total, g);
-    if (window_len != g.N || twiddles_len != (1 << g.log_nfft) || band_weights_len < 0 || s.Fcap > 0x7fffffffL)
-        return DCS_ERR_BADARG;
-    if (workspace_bytes < s.bytes) return DCS_ERR_WORKSPACE;
-    char* ws = static_cast<char*>(workspace);
-    long* fbase = reinterpret_cast<long*>(ws);
-    double* vals = reinterpret_cast<double*>(ws + s.off_vals);
-    int* valid = reinterpret_cast<int*>(ws + s.off_valid);
-    hipStream_t st = dcs_stream(stream);
-    DCS_LAUNCH(ragged_prefix_kernel<PrefixSpectralFrames>, dim3(1), dim3(256), 0, st, offsets, n, total,
-               PrefixSpectralFrames{g.N, g.S}, s.Fcap, fbase);
-    DCS_CHECK_LAUNCH();
+    if (bad_rate(fs) || !band_first || !band_offset || !band_weights || !twiddles || !out_wss || !out_fwssnr) return DCS_ERR_BADARG;
+    const int log = log_nfft(frame_geometry(fs).N);
+    if (twiddles_len != (1 << log) || band_weights_len < 0) return DCS_ERR_BADARG;
+    FrameGeometry g;
+    FrameLayout s;
+    hipStream_t st;
+    const int rc = frame_slots_begin(clean, est, offsets, n, total, fs, window, window_len, 2, workspace, workspace_bytes, stream,
+                                     &g, &s, &st);
+    if (rc != DCS_OK) return rc;
     if (s.Fcap > 0) {
-        switch (g.log_nfft) {
-            case 9: launch_frames<9>(s, st, clean, est, offsets, n, total, fbase, window, g, band_first, band_offset, band_weights,
-                                     band_weights_len, twiddles, vals, valid); break;
-            case 10: launch_frames<10>(s, st, clean, est, offsets, n, total, fbase, window, g, band_first, band_offset, band_weights,
-                                       band_weights_len, twiddles, vals, valid); break;
-            case 11: launch_frames<11>(s, st, clean, est, offsets, n, total, fbase, window, g, band_first, band_offset, band_weights,
-                                       band_weights_len, twiddles, vals, valid); break;
-            default: launch_frames<12>(s, st, clean, est, offsets, n, total, fbase, window, g, band_first, band_offset, band_weights,
-                                       band_weights_len, twiddles, vals, valid); break;
+        switch (log) {
+            case 9: launch_frames<9>(s, st, clean, est, offsets, n, total, window, g, band_first, band_offset, band_weights,
+                                     band_weights_len, twiddles); break;
+            case 10: launch_frames<10>(s, st, clean, est, offsets, n, total, window, g, band_first, band_offset, band_weights,
+                                       band_weights_len, twiddles); break;
+            case 11: launch_frames<11>(s, st, clean, est, offsets, n, total, window, g, band_first, band_offset, band_weights,
+                                       band_weights_len, twiddles); break;
+            default: launch_frames<12>(s, st, clean, est, offsets, n, total, window, g, band_first, band_offset, band_weights,
+                                       band_weights_len, twiddles); break;
         }
         DCS_CHECK_LAUNCH();
     }
-    DCS_LAUNCH(spectral_recording_kernel, dim3(n), dim3(256), 0, st, fbase, s.Fcap, vals, valid, out_wss, out_fwssnr);
+    DCS_LAUNCH(spectral_recording_kernel, dim3(n), dim3(256), 0, st, s.fbase, s.Fcap, s.vals, s.valid, out_wss, out_fwssnr);
     DCS_CHECK_LAUNCH();
     return DCS_OK;
 }

@@ -5,6 +5,7 @@
 // scores it: dcs_stoi_ragged_f32 is bit-equal to dcs_stoi_f32 with B = 1 on the same samples.
 #pragma once
 #include "fft512_common.h"
+#include "ragged_common.h"
 
 namespace dcs_stoi {
 
@@ -19,7 +20,7 @@ constexpr double kPi = 3.141592653589793;
 // frames of range(0, L - 256, 128): both framings of the host function
 __host__ __device__ inline long stoi_frames(long L) { return L > kFrame ? (L - kFrame + kHop - 1) / kHop : 0; }
 
-inline long align256(long n) { return (n + 255) & ~255L; }
+using dcs_ragged::align256;                                  // the one definition of the ragged / STOI family
 
 // hanning(258)[1:-1]
 __device__ __forceinline__ double hann256(int n) { return 0.5 - 0.5 * cos(2.0 * kPi * (double)(n + 1) / 257.0); }

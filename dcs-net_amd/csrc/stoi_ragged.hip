@@ -3,12 +3,12 @@
 // reference's SiSNR (network_functions.py:30-42) per recording.  What stoi.hip's kernels do to one row, these do to one
 // recording, through the same device functions (stoi_common.h): a recording's score is bit-equal to dcs_stoi_f32 with B = 1.
 //
-//   ragged_prefix_kernel          (ragged_common.h, shared with frame_measures.hip) one workgroup: out[i] = sum over j < i of v_j, v_j = the resampled length ceil(L_j up / down) or the
+//   ragged_prefix_kernel          (ragged_common.h) one workgroup: out[i] = sum over j < i of v_j, v_j = the resampled length ceil(L_j up / down) or the
 //                                   frame count of recording j, clamped to the capacity the host sized the buffers for — the
 //                                   later kernels take every per-recording size from the differences of this table, so no
 //                                   value in offsets[] makes them write outside their buffers
 //   resample_poly_ragged_kernel   resample_poly_kernel, one thread per output sample of the flat output; a thread finds its
-//                                   recording by bisection of the output offsets (as resample_sinc_kernel does); taps stop at the
+//                                   recording by owner() of the output offsets (as resample_sinc_kernel does); taps stop at the
 //                                   recording's own ends
 //   stoi_keep_ragged_kernel       one workgroup per recording: stoi_keep_kernel on its samples and frame slots
 //   stoi_bands_ragged_kernel      grid (frames of the LONGEST recording / 4, 2 n): stoi_bands_kernel; workgroups past a recording's
@@ -32,7 +32,7 @@
 namespace {
 
 using namespace dcs_stoi;
-using namespace dcs_ragged;                                  // rec_span, ragged_prefix_kernel, block_sum, bad_ragged
+using namespace dcs_ragged;                                  // owner, rec_span, ragged_prefix_kernel, block_sum, bad_ragged
 
 constexpr int kMaxRatio = 1 << 16;                           // up, down: total * up and n_out * down stay inside int64
 constexpr double kSisnrEps = 1e-8;                           // SiSNR.__call__'s default, network_functions.py:31
@@ -52,11 +52,7 @@ __global__ __launch_bounds__(256) void resample_poly_ragged_kernel(const float* 
                                                                    const float* __restrict__ h, int taps, int up, int down) {
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     if (g >= y_off[n]) return;
-    int lo = 0, hi = n;                                      // y_off[lo] <= g < y_off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (y_off[mid] <= g) lo = mid; else hi = mid;
-    }
+    const int lo = owner(y_off, n, g);
     long first;
     const long L = rec_span(offsets, lo, total, &first);
     y[g] = resample_poly_sample(x + first, L, g - y_off[lo], h, taps, up, down);

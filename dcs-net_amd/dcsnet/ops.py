@@ -1494,13 +1494,34 @@ def sisnr_ragged(clean, est, offsets):
     return out
 
 
+def _measures_workspace_bytes(what, n, total, fs):
+    nbytes = getattr(_lib.load(), f'dcs_{what}_workspace_bytes')(int(n), int(total), int(fs))
+    if nbytes < 0:
+        raise _lib.DcsHipError(f'{what}: unsupported arguments ({n} recordings, {total} samples, fs={fs}; the rate must lie in '
+                               f'8000 .. 48000)')
+    return nbytes
+
+
+def _chk_measure_buffers(what, out, count, n, dev, nbytes, workspace):
+    """The buffers a measure call writes: out, `count` float32 [n] tensors (made here when None), and the workspace, uint8
+    (nbytes made here when None; its size is checked by the library).  -> (out, workspace)."""
+    if out is None:
+        out = tuple(torch.empty(n, dtype=torch.float32, device=dev) for _ in range(count))
+    if len(out) != count:
+        raise _lib.DcsHipError(f'{what}: out must be {count} float32 [{n}] tensors on {dev}')
+    for o in out:
+        _chk(o, f'{what}: out', 1)
+        if o.numel() != n or o.device != dev:
+            raise _lib.DcsHipError(f'{what}: out must be {count} float32 [{n}] tensors on {dev}')
+    ws = _workspace(nbytes, dev) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
+        raise _lib.DcsHipError(f'{what}: workspace must be a contiguous uint8 tensor on {dev}')
+    return tuple(out), ws
+
+
 def frame_measures_workspace_bytes(n, total, fs):
     """The workspace of frame_measures_ragged for n recordings of `total` samples together at rate fs (host arithmetic)."""
-    nbytes = _lib.load().dcs_frame_measures_ragged_workspace_bytes(int(n), int(total), int(fs))
-    if nbytes < 0:
-        raise _lib.DcsHipError(f'frame_measures_ragged: unsupported arguments ({n} recordings, {total} samples, fs={fs}; the rate '
-                               f'must lie in 8000 .. 48000)')
-    return nbytes
+    return _measures_workspace_bytes('frame_measures_ragged', n, total, fs)
 
 
 def frame_measures_ragged(clean, est, offsets, fs, window=None, out=None, workspace=None):
@@ -1518,29 +1539,17 @@ def frame_measures_ragged(clean, est, offsets, fs, window=None, out=None, worksp
         window = measure_window(fs, dev)
     if window.dtype != torch.float64 or window.dim() != 1 or not window.is_contiguous() or window.device != dev:
         raise _lib.DcsHipError(f'frame_measures_ragged: window must be a contiguous float64 [N] tensor on {dev}')
-    if out is None:
-        out = tuple(torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
-    for o in out:
-        _chk(o, 'frame_measures_ragged: out', 1)
-        if o.numel() != n or o.device != dev:
-            raise _lib.DcsHipError(f'frame_measures_ragged: out must be three float32 [{n}] tensors on {dev}')
-    ws = _workspace(nbytes, dev) if workspace is None else workspace
-    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
-        raise _lib.DcsHipError(f'frame_measures_ragged: workspace must be a contiguous uint8 tensor on {dev}')
+    out, ws = _chk_measure_buffers('frame_measures_ragged', out, 3, n, dev, nbytes, workspace)
     sig = (ptr(clean), ptr(est)) if total else (None, None)
     check(_lib.load().dcs_frame_measures_ragged_f32(*sig, ptr(offsets), n, total, fs, ptr(window), window.numel(), ptr(out[0]),
                                                     ptr(out[1]), ptr(out[2]), ptr(ws), ws.numel(), cur_stream()),
           'dcs_frame_measures_ragged_f32')
-    return tuple(out)
+    return out
 
 
 def spectral_measures_workspace_bytes(n, total, fs):
     """The workspace of spectral_measures_ragged for n recordings of `total` samples together at rate fs (host arithmetic)."""
-    nbytes = _lib.load().dcs_spectral_measures_ragged_workspace_bytes(int(n), int(total), int(fs))
-    if nbytes < 0:
-        raise _lib.DcsHipError(f'spectral_measures_ragged: unsupported arguments ({n} recordings, {total} samples, fs={fs}; the '
-                               f'rate must lie in 8000 .. 48000)')
-    return nbytes
+    return _measures_workspace_bytes('spectral_measures_ragged', n, total, fs)
 
 
 def spectral_measures_ragged(clean, est, offsets, fs, out=None, workspace=None):
@@ -1555,17 +1564,7 @@ def spectral_measures_ragged(clean, est, offsets, fs, out=None, workspace=None):
     nbytes = spectral_measures_workspace_bytes(n, total, fs)
     from .metrics import spectral_tables
     window, band_first, band_offset, band_weights, twiddles = spectral_tables(fs, dev)
-    if out is None:
-        out = tuple(torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
-    if len(out) != 2:
-        raise _lib.DcsHipError(f'spectral_measures_ragged: out must be two float32 [{n}] tensors on {dev}')
-    for o in out:
-        _chk(o, 'spectral_measures_ragged: out', 1)
-        if o.numel() != n or o.device != dev:
-            raise _lib.DcsHipError(f'spectral_measures_ragged: out must be two float32 [{n}] tensors on {dev}')
-    ws = _workspace(nbytes, dev) if workspace is None else workspace
-    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
-        raise _lib.DcsHipError(f'spectral_measures_ragged: workspace must be a contiguous uint8 tensor on {dev}')
+    out, ws = _chk_measure_buffers('spectral_measures_ragged', out, 2, n, dev, nbytes, workspace)
     sig = (ptr(clean), ptr(est)) if total else (None, None)
     check(_lib.load().dcs_spectral_measures_ragged_f32(*sig, ptr(offsets), n, total, fs, ptr(window), window.numel(),
                                                        ptr(band_first), ptr(band_offset), ptr(band_weights),

@@ -267,6 +267,8 @@ def test_argument_errors(dev):
         metrics.frame_measures_ragged(xd, xd, [0, 800, 1999], 16000)               # host offsets are checked
     with pytest.raises(_lib.DcsHipError):
         ops.frame_measures_ragged(xd, xd, off.to(dev), 16000, window=torch.ones(480, device=dev))       # float32 window
+    with pytest.raises(_lib.DcsHipError):
+        ops.frame_measures_ragged(xd, xd, off.to(dev), 16000, out=tuple(torch.empty(2, device=dev) for _ in range(4)))  # 4 for 3
     got = metrics.frame_measures_ragged(xd, xd, off, 16000)                         # digital silence
     assert bool((got['ssnr'] == -10.0).all()) and bool(torch.isnan(got['llr']).all()) and bool(torch.isnan(got['cd']).all())
 
