@@ -174,6 +174,8 @@ SIGNATURES = {
     'dcs_frame_measures_ragged_f32': (_I, [_P, _P, _P, _I, _L, _I, _P, _I, _P, _P, _P, _P, _L, _P]),
     'dcs_spectral_measures_ragged_workspace_bytes': (_L, [_I, _L, _I]),
     'dcs_spectral_measures_ragged_f32': (_I, [_P, _P, _P, _I, _L, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _L, _P]),
+    'dcs_sdr_ragged_workspace_bytes': (_L, [_I, _L, _I]),
+    'dcs_sdr_ragged_f32': (_I, [_P, _P, _P, _P, _I, _L, _I, _P, _P, _P, _L, _P]),
     'dcs_val_accumulate_f32': (_I, [_P, _I, _P, _I, _I, _P, _P]),
     'dcs_resample_sinc_f32':(_I, [_P, _P, _P, _P, _I, _L, _P, _I, _I, _I, _P]),
     'dcs_audio_stft_batch_f32': (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P]),

@@ -1,5 +1,5 @@
-"""How good is an enhanced recording: STOI, SI-SNR and (on request) ESTOI, segmental SNR, LLR, cepstrum distance, WSS and
-frequency-weighted segmental SNR of whole recordings, scored where the Enhancer leaves them.
+"""How good is an enhanced recording: STOI, SI-SNR and (on request) ESTOI, segmental SNR, LLR, cepstrum distance, WSS,
+frequency-weighted segmental SNR and the BSS-eval SDR of whole recordings, scored where the Enhancer leaves them.
 
     scorer = RecordingScorer(Enhancer(net, mode='dcs'))          (or a MagnitudeEnhancer)
     scores = scorer.score(noisy_waves, clean_waves, sample_rate=48000)
@@ -15,6 +15,9 @@ frequency-weighted segmental SNR of whole recordings, scored where the Enhancer 
     scorer.spectral_measures = True                               the dict gains 'wss', 'fwssnr' and their _noisy twins: weighted
         spectral slope and frequency-weighted segmental SNR (dB) (Hu & Loizou; metrics.spectral_measures), at config.sr, from
         two more calls (metrics.spectral_measures_ragged, csrc/spectral_measures.hip)
+    scorer.sdr = True                                             the dict gains 'sdr', 'sdr_noisy': the BSS-eval signal-to-
+        distortion ratio (dB; metrics.sdr, 512 taps), from ONE more call that scores the enhanced and the unprocessed signal
+        against the same clean buffer (metrics.sdr_ragged with estimate2, csrc/sdr_ragged.hip)
 
 The Enhancer keeps everything ragged in one flat device buffer with an int64 offset table; the metrics speak the same
 convention (metrics.stoi_ragged / sisnr_ragged, csrc/stoi_ragged.hip), so a whole test set is scored in a handful of launches
@@ -35,13 +38,15 @@ class RecordingScorer:
     """enhancer: an Enhancer or a MagnitudeEnhancer, used as it is configured (mode, segment geometry, graph).  extended: score
     ESTOI as well.  The attribute frame_measures (default False; the constructor keeps its two arguments): score segmental SNR,
     LLR and cepstrum distance as well.  The attribute spectral_measures (default False, likewise): score WSS and the
-    frequency-weighted segmental SNR as well.  self.metrics names the dict's keys: METRICS, then EXTENDED, then FRAME_MEASURES,
-    then SPECTRAL_MEASURES where asked for."""
+    frequency-weighted segmental SNR as well.  The attribute sdr (default False, likewise): score the BSS-eval SDR as well.
+    self.metrics names the dict's keys: METRICS, then EXTENDED, then FRAME_MEASURES, then SPECTRAL_MEASURES, then SDR where
+    asked for."""
 
     METRICS = ('stoi', 'stoi_noisy', 'sisnr', 'sisnr_noisy')
     EXTENDED = ('estoi', 'estoi_noisy')
     FRAME_MEASURES = ('ssnr', 'ssnr_noisy', 'llr', 'llr_noisy', 'cd', 'cd_noisy')
     SPECTRAL_MEASURES = ('wss', 'wss_noisy', 'fwssnr', 'fwssnr_noisy')
+    SDR = ('sdr', 'sdr_noisy')
 
     def __init__(self, enhancer, extended=False):
         if not isinstance(enhancer, Enhancer):
@@ -50,13 +55,15 @@ class RecordingScorer:
         self.extended = bool(extended)
         self.frame_measures = False                          # set it to True on the scorer: the constructor's arguments are pinned
         self.spectral_measures = False                       # likewise
+        self.sdr = False                                     # likewise
         self._clean = None                                   # the clean recordings at config.sr, capacity kept across calls
 
     @property
     def metrics(self):
         return (self.METRICS + (self.EXTENDED if self.extended else ()) +
                 (self.FRAME_MEASURES if self.frame_measures else ()) +
-                (self.SPECTRAL_MEASURES if self.spectral_measures else ()))
+                (self.SPECTRAL_MEASURES if self.spectral_measures else ()) +
+                (self.SDR if self.sdr else ()))
 
     @staticmethod
     def _check_pairs(noisy_waves, clean_waves):
@@ -108,6 +115,8 @@ class RecordingScorer:
             unprocessed = metrics.spectral_measures_ragged(clean, noisy, offsets, enh.sr, longest=longest)
             for k in ('wss', 'fwssnr'):                      # the order of SPECTRAL_MEASURES
                 scores[k], scores[k + '_noisy'] = enhanced[k], unprocessed[k]
+        if self.sdr:
+            scores['sdr'], scores['sdr_noisy'] = metrics.sdr_ragged(clean, speech, offsets, estimate2=noisy)
         if return_audio:
             return scores, enh._split(plan, speech)
         return scores
@@ -131,7 +140,9 @@ def summarise(scores):
     (enhanced - noisy, as for the others), llr_improvement and cd_improvement — these two are noisy - enhanced, because a
     lower LLR or cepstrum distance is the better one, so a positive improvement always means the network helped.  With the
     spectral-measure keys in the dict (RecordingScorer.SPECTRAL_MEASURES): their four columns behind those, wss_improvement
-    (noisy - enhanced: lower is better) and fwssnr_improvement (enhanced - noisy)."""
+    (noisy - enhanced: lower is better) and fwssnr_improvement (enhanced - noisy).  With 'sdr' and 'sdr_noisy' in the dict
+    (RecordingScorer.SDR): their two columns behind those and sdr_improvement (enhanced - noisy; a pair of equal
+    infinities is left out of its mean like a NaN)."""
     keys = RecordingScorer.METRICS
     extended = all(k in scores for k in RecordingScorer.EXTENDED)
     if extended:
@@ -142,6 +153,9 @@ def summarise(scores):
     spectral = all(k in scores for k in RecordingScorer.SPECTRAL_MEASURES)
     if spectral:
         keys = keys + RecordingScorer.SPECTRAL_MEASURES
+    sdr = all(k in scores for k in RecordingScorer.SDR)
+    if sdr:
+        keys = keys + RecordingScorer.SDR
     table = torch.stack([scores[k].to(torch.float32) for k in keys], dim=1).cpu().numpy()
 
     def mean(v):
@@ -165,4 +179,8 @@ def summarise(scores):
         j = keys.index('wss')
         out['wss_improvement'] = mean(table[:, j + 1] - table[:, j])
         out['fwssnr_improvement'] = mean(table[:, j + 2] - table[:, j + 3])
+    if sdr:
+        j = keys.index('sdr')
+        with np.errstate(invalid='ignore'):                  # inf - inf -> NaN: left out of the mean
+            out['sdr_improvement'] = mean(table[:, j] - table[:, j + 1])
     return out, table

@@ -48,6 +48,12 @@ independent routes).  On the device it is `spectral_measures_ragged()` (csrc/spe
 tests/test_spectral_measures_device.py).  `composite_measures()` is Hu & Loizou's CSIG / CBAK / COVL regression on PESQ,
 LLR, WSS and segmental SNR; the PESQ values come from the caller.
 
+BSS-eval SDR.  `sdr()` restates the signal-to-distortion ratio of Vincent, Gribonval & Fevotte (2006) as
+`mir_eval.separation.bss_eval_sources` computes it for one source: the estimate projected onto 512 delayed copies of the
+reference (Toeplitz normal equations by a Levinson recursion written out here, both energies summed explicitly).  PARITY
+UNPINNED, as for STOI: mir_eval is not here; tests/test_sdr_cpu.py checks a brute-force projection, two other solvers and the
+defining properties.  On the device it is `sdr_ragged()` (csrc/sdr_ragged.hip, fp64; tests/test_sdr_device.py).
+
 Active speech level.  `active_speech_level()` restates ITU-T P.56 method B after the published `asl_P56` of Hu & Loizou (two
 one-pole envelope smoothers, 15 power-of-two thresholds with a 0.2 s hangover, the 15.9 dB margin), taking the margin crossing
 itself where the published code bisects to 0.5 dB.  PARITY UNPINNED, as for STOI; tests/test_active_level_cpu.py checks the
@@ -680,6 +686,105 @@ def spectral_measures_ragged(clean, estimate, offsets, fs, longest=None):
     clean, estimate, offsets, _ = _ragged_args('spectral_measures_ragged', clean, estimate, offsets, longest)
     w, f = ops.spectral_measures_ragged(clean, estimate, offsets, fs)
     return {'wss': w, 'fwssnr': f}
+
+
+# ---- the signal-to-distortion ratio of BSS-eval ---------------------------------------------------------------------------------
+
+SDR_FILTER_LENGTH = 512         # bss_eval_sources' flen
+
+
+def sdr_correlations(x, y, filter_length=SDR_FILTER_LENGTH):
+    """(R [K], D [K]) of 1-D float64 signals of equal length L: R[k] = sum_t x[t] x[t + k], D[k] = sum_t x[t] y[t + k] over
+    the samples that exist (0 for k >= L)."""
+    L, K = len(x), int(filter_length)
+    R, D = np.zeros(K), np.zeros(K)
+    for k in range(min(K, L)):
+        R[k] = np.dot(x[:L - k], x[k:])
+        D[k] = np.dot(x[:L - k], y[k:])
+    return R, D
+
+
+def toeplitz_levinson(R, D):
+    """Solve the symmetric Toeplitz system T(R) c = D (T[i, j] = R[|i - j|]) by the Levinson recursion in fp64 -> (c [K], E [K]):
+    E[m] is the forward prediction error energy after step m (E[0] = R[0]); the recursion stops at the first E[m] that is not a
+    positive finite number, leaving the rest of E as NaN (c is then meaningless)."""
+    R, D = np.asarray(R, dtype=np.float64), np.asarray(D, dtype=np.float64)
+    K = len(R)
+    a, c, E = np.zeros(K), np.zeros(K), np.full(K, np.nan)      # a[1 .. m - 1]: the forward predictor of order m - 1
+    E[0] = R[0]
+    if not (E[0] > 0 and np.isfinite(E[0])):
+        return c, E
+    c[0] = D[0] / R[0]
+    with np.errstate(all='ignore'):
+        for m in range(1, K):
+            kappa = (R[m] - np.dot(a[1:m], R[m - 1:0:-1])) / E[m - 1]
+            a[1:m] = a[1:m] - kappa * a[m - 1:0:-1]
+            a[m] = kappa
+            E[m] = E[m - 1] * (1.0 - kappa * kappa)
+            if not (E[m] > 0 and np.isfinite(E[m])):
+                return c, E
+            delta = (D[m] - np.dot(c[:m], R[m:0:-1])) / E[m]
+            c[:m] -= delta * a[m:0:-1]
+            c[m] = delta
+    return c, E
+
+
+def sdr_from_filter(x, y, c):
+    """10 log10(sum s^2 / sum (y_pad - s)^2) with s = c * x on its L + K - 1 positions and y padded with K - 1 zeros: both
+    energies summed explicitly (num = c'D and den = |y|^2 - c'D cancel at high SDR).  +inf for den == 0 < num; NaN when either
+    energy is not finite or both are 0."""
+    x, y, c = (np.asarray(v, dtype=np.float64) for v in (x, y, c))
+    with np.errstate(all='ignore'):
+        s = np.convolve(x, c)
+        e = -s
+        e[:len(y)] += y
+        num, den = float(np.dot(s, s)), float(np.dot(e, e))
+        if not (np.isfinite(num) and np.isfinite(den)) or (num == 0.0 and den == 0.0):
+            return float('nan')
+        if den == 0.0:
+            return float('inf')
+        return float(10.0 * np.log10(num / den))
+
+
+def sdr(x, y, filter_length=SDR_FILTER_LENGTH):
+    """The signal-to-distortion ratio of BSS-eval (E. Vincent, R. Gribonval, C. Fevotte, "Performance Measurement in Blind Audio
+    Source Separation", IEEE TASLP 14(4), 2006) of the estimate y against the reference x (1-D, equal length L, taken as
+    float64), in dB: y is projected onto the span of the K = filter_length (1 .. 512) delayed copies x[t - k], k < K, and the
+    energy of the projection s is set against the energy of y - s.  R, D: sdr_correlations; the filter c: toeplitz_levinson;
+    the energies: sdr_from_filter.  In exact arithmetic this is mir_eval.separation.bss_eval_sources for one source (SDR = SAR,
+    SIR = +inf, flen = 512).  Unlike SI-SNR, which forgives a gain only, it forgives any filter of up to K taps between the two
+    signals, a delay among them.  +inf when the residual is exactly 0; NaN for L == 0, for an all-zero x or y (mir_eval raises
+    there), for an input that is not finite, and when an error energy E_m of the recursion is <= 0 or not finite.  PARITY
+    UNPINNED, as for STOI: neither mir_eval nor museval is here to compare with; tests/test_sdr_cpu.py checks it against a
+    brute-force least-squares projection, two other solvers and its defining properties."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    K = int(filter_length)
+    if x.shape != y.shape or x.ndim != 1:
+        raise ValueError(f'sdr: x {x.shape} and y {y.shape} must be 1-D signals of equal length')
+    if not 1 <= K <= SDR_FILTER_LENGTH:
+        raise ValueError(f'sdr: filter_length={filter_length} (1 .. {SDR_FILTER_LENGTH})')
+    if len(x) == 0 or not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))) or not x.any() or not y.any():
+        return float('nan')
+    c, E = toeplitz_levinson(*sdr_correlations(x, y, K))
+    if not np.all(E > 0):                                    # NaN where the recursion stopped
+        return float('nan')
+    return sdr_from_filter(x, y, c)
+
+
+def sdr_ragged(clean, estimate, offsets, filter_length=SDR_FILTER_LENGTH, estimate2=None):
+    """sdr(clean[a:b], estimate[a:b], filter_length) for every recording [a, b) = offsets[i:i + 2] of two flat device buffers: a
+    float32 [n] device tensor (NaN and +inf where the host function has them), fp64 until that rounding, in four launches
+    whatever n is (csrc/sdr_ragged.hip) and without a host read-back (capturable when offsets are on the device).  A
+    recording's value is bit-equal to that recording scored alone.  estimate2: a second estimate against the same clean buffer
+    (the unprocessed signal beside the enhanced one) in the same launches -> the pair of tensors, each bit-equal to a call of
+    its own; the correlation of the clean signal and the forward recursion are shared.  The measure is rate-free.  offsets: as
+    for stoi_ragged.  CPU signals raise DcsHipError."""
+    from . import ops
+    clean, estimate, offsets, _ = _ragged_args('sdr_ragged', clean, estimate, offsets, None)
+    if estimate2 is None:
+        return ops.sdr_ragged(clean, estimate, offsets, filter_length=filter_length)
+    _, estimate2, _, _ = _ragged_args('sdr_ragged', clean, estimate2, offsets, None)
+    return ops.sdr_ragged(clean, estimate, offsets, est2=estimate2, filter_length=filter_length)
 
 
 # ---- ITU-T P.56 active speech level (method B) -------------------------------------------------------------------------------------

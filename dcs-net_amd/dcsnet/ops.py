@@ -1574,6 +1574,41 @@ def spectral_measures_ragged(clean, est, offsets, fs, out=None, workspace=None):
     return tuple(out)
 
 
+SDR_CHUNK = 2048                # csrc/sdr_ragged.hip::kChunk: the positions of a recording one workgroup takes
+SDR_MAX_TAPS = 512
+SDR_LAUNCHES = 4                # correlation partials, solve, projection, finish: whatever n is
+
+
+def sdr_workspace_bytes(n, total, filter_length=SDR_MAX_TAPS):
+    """The workspace of sdr_ragged for n recordings of `total` samples together and filter_length taps (host arithmetic)."""
+    nbytes = _lib.load().dcs_sdr_ragged_workspace_bytes(int(n), int(total), int(filter_length))
+    if nbytes < 0:
+        raise _lib.DcsHipError(f'sdr_ragged: unsupported arguments ({n} recordings, {total} samples, filter_length='
+                               f'{filter_length}; it must lie in 1 .. {SDR_MAX_TAPS})')
+    return nbytes
+
+
+def sdr_ragged(clean, est, offsets, est2=None, filter_length=SDR_MAX_TAPS, out=None, workspace=None):
+    """The BSS-eval signal-to-distortion ratio of n recordings of different lengths: clean / est float [total], offsets int64
+    [n + 1] on the device -> float [n] dB, metrics.sdr per recording in fp64 (dcs_sdr_ragged_f32: four launches whatever n is).
+    est2: a second estimate against the same clean buffer in the same launches -> the pair (sdr of est, sdr of est2), each
+    bit-equal to a call of its own.  out (one float32 [n] tensor per estimate) and workspace (uint8, at least
+    sdr_workspace_bytes) let a caller own the buffers the call writes."""
+    signals = (clean, est) if est2 is None else (clean, est, est2)
+    n, total = _chk_ragged('sdr_ragged', offsets, *signals)
+    dev = clean.device
+    filter_length = int(filter_length)
+    nbytes = sdr_workspace_bytes(n, total, filter_length)
+    out, ws = _chk_measure_buffers('sdr_ragged', out, len(signals) - 1, n, dev, nbytes, workspace)
+    sig = [ptr(s) if total else None for s in signals] + [None] * (3 - len(signals))
+    if est2 is not None and not total:
+        sig[2] = ptr(out[1])                                 # an empty buffer has no address; only est2's being set is read
+    check(_lib.load().dcs_sdr_ragged_f32(*sig, ptr(offsets), n, total, filter_length, ptr(out[0]),
+                                         None if est2 is None else ptr(out[1]), ptr(ws), ws.numel(), cur_stream()),
+          'dcs_sdr_ragged_f32')
+    return out[0] if est2 is None else tuple(out)
+
+
 # ---- HBM-resident training audio (csrc/audio_store.hip, dcsnet/audio_store.py) ----------------------------------------
 
 _SINC_LOWPASS_WIDTH, _SINC_ROLLOFF = 6, 0.99                 # torchaudio 0.9.0's Resample defaults (config.py:61)

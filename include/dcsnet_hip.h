@@ -975,6 +975,27 @@ int dcs_spectral_measures_ragged_f32(const float* clean, const float* est, const
                                      dcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Signal-to-distortion ratio of BSS-eval (bss_eval_sources for one source, as dcsnet/metrics.py::sdr restates it: that host
+ * function is the numerics contract) of whole recordings, sdr_ragged.hip, in the ragged convention above (same limits on n and
+ * total, same clamping of the offsets).  The measure is rate-free.  K = filter_length, 1 <= K <= 512 (anything else:
+ * DCS_ERR_BADARG): R[k] = sum_t x[t] x[t + k] and D[k] = sum_t x[t] y[t + k] over the samples that exist, T(R) c = D by the
+ * Levinson recursion, s = c * x on the L + K - 1 positions, 10 log10(sum s^2 / sum (y_pad - s)^2) with both energies summed
+ * explicitly.  Recordings are cut into chunks of 2048 positions counted from their own first sample.
+ * dcs_sdr_ragged_workspace_bytes: pure host arithmetic, correlation partials double[Cc][3][K] | filters double[n][2][K] |
+ *   validity int[n] | energy partials double[Cc][2][2], Cc = total / 2048 + 2 n chunk slots; it does not decrease in n, total
+ *   or K; < 0 for bad arguments.
+ * dcs_sdr_ragged_f32: out float[n] = the SDR of est against clean in dB; +inf when the residual energy is 0 and the projected
+ *   energy is not; NaN for a recording without samples, with an all-zero clean or estimated signal, with a sample that is
+ *   not finite, or whose recursion meets an error energy E_m that is <= 0 or not finite.  est2 / out2: a second estimate
+ *   scored against the same clean signal in the same launches (R and the forward recursion are shared), both set or both
+ *   null; out2[i] is bit-equal to a call of its own with est2 as est.  Every sum in fp64 in a fixed order, one rounding to
+ *   float at the end.  Four launches whatever n is; no atomics, no sync, no read-back (capturable, bit-reproducible); a
+ *   recording's value is bit-equal to that recording scored alone. */
+long dcs_sdr_ragged_workspace_bytes(int n, long total, int filter_length);
+int dcs_sdr_ragged_f32(const float* clean, const float* est, const float* est2, const long* offsets, int n, long total,
+                       int filter_length, float* out, float* out2, void* workspace, long workspace_bytes, dcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * The books of a validation epoch on the device (dcsnet/validation.py), validation.hip: one launch per batch folds the batch
  * into `state`, so an epoch ends with one host read.  losses: device float[n_loss], n_loss = 3 (noise, speech, total) or 1
  * (speech); the MONITORED loss is losses[n_loss - 1].  scores: device float[n_scores][B], 0 <= n_scores <= DCS_VAL_MAX_SCORES,

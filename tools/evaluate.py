@@ -12,6 +12,8 @@ many were not), and the mean improvements stoi - stoi_noisy and sisnr - sisnr_no
 ssnr_improvement, llr_improvement, cd_improvement; the last two are noisy - enhanced: lower is better).
 --spectral-measures adds the weighted spectral slope and the frequency-weighted segmental SNR (wss, fwssnr, their _noisy twins,
 wss_improvement = noisy - enhanced, fwssnr_improvement).
+--sdr adds the signal-to-distortion ratio of BSS-eval (mir_eval's bss_eval_sources for one source, 512 taps: sdr, sdr_noisy,
+sdr_improvement); beside sisnr it tells filtering from noise, since it forgives a short filter where SI-SNR forgives a gain.
 --pesq-csv FILE takes PESQ values computed elsewhere, one line `name,pesq[,pesq_noisy]` per file of the set (name: the WAV
 file's name, with or without .wav; '#' lines and a `name,pesq...` header line are skipped), implies --frame-measures and
 --spectral-measures, and adds Hu & Loizou's composite measures csig, cbak, covl (metrics.composite_measures) to the JSON line
@@ -102,6 +104,7 @@ def main():
                     help='score segmental SNR, LLR and cepstrum distance (Hu & Loizou) as well')
     ap.add_argument('--spectral-measures', action='store_true',
                     help='score the weighted spectral slope and the frequency-weighted segmental SNR (Hu & Loizou) as well')
+    ap.add_argument('--sdr', action='store_true', help='score the BSS-eval signal-to-distortion ratio (512 taps) as well')
     ap.add_argument('--pesq-csv', default=None,
                     help='name,pesq[,pesq_noisy] lines: add CSIG, CBAK and COVL (implies --frame-measures --spectral-measures)')
     ap.add_argument('--segment-frames', type=int, default=2000)
@@ -138,6 +141,7 @@ def main():
     scorer = RecordingScorer(enh, extended=a.extended)
     scorer.frame_measures = a.frame_measures
     scorer.spectral_measures = a.spectral_measures
+    scorer.sdr = a.sdr
     summary, table = summarise(scorer.score_files(noisy, clean))
     keys = scorer.metrics
     if pesq is not None:

@@ -21,12 +21,20 @@ profiles/frame_measures_bench.json.
 csrc/spectral_measures.hip): its device pass beside the STOI pass and the frame-measures pass, the three alternating in the same
 rounds, the host function metrics.spectral_measures and the largest differences -> profiles/spectral_measures_bench.json.
 
+--sdr does the same for metrics.sdr_ragged (the BSS-eval signal-to-distortion ratio, 512 taps; csrc/sdr_ragged.hip): its device
+pass with one estimate and with two estimates in one call beside the STOI pass, the three alternating in the same rounds, the
+host function metrics.sdr and the largest difference -> profiles/sdr_bench.json.  --kernel-stats FILE folds in the kernel times
+of a rocprofv3 --kernel-trace --stats run of this tool (taken in a run of its own): the share of the solve launch.
+
 usage: python tools/score_bench.py [--out profiles/score_bench.json] [--recordings 32] [--extended] [--parent-json FILE]
        python tools/score_bench.py --frame-measures [--out profiles/frame_measures_bench.json] [--recordings 32]
-       python tools/score_bench.py --spectral-measures [--out profiles/spectral_measures_bench.json] [--recordings 32]"""
+       python tools/score_bench.py --spectral-measures [--out profiles/spectral_measures_bench.json] [--recordings 32]
+       python tools/score_bench.py --sdr [--out profiles/sdr_bench.json] [--recordings 32] [--kernel-stats FILE]"""
 import argparse
+import csv
 import json
 import os
+import re
 import sys
 import time
 
@@ -168,11 +176,91 @@ def spectral_measures_bench(a, c, e, off, off_h, longest, fs):
     return res
 
 
+FP64_VECTOR_PEAK = 78.6e12      # FLOP/s: half the FP32 vector peak of MI355X_MICROARCH (157.3 TFLOPS), AMD's published fp64 figure
+
+
+def sdr_kernel_times(path):
+    """{'one_estimate' | 'two_estimates': {pass: mean microseconds per launch}} of the sdr_<pass>_kernel<...> rows of a rocprofv3
+    kernel-stats CSV (the last template argument is the number of estimates; of signals, one more, for the corr pass)."""
+    out = {'one_estimate': {}, 'two_estimates': {}}
+    with open(path, newline='') as f:
+        for row in csv.DictReader(f):
+            m = re.search(r'sdr_(\w+)_kernel<([\d, ]+)>', row.get('Name') or row.get('KernelName') or '')
+            if not m:
+                continue
+            estimates = int(m.group(2).split(',')[-1]) - (m.group(1) == 'corr')
+            out['one_estimate' if estimates == 1 else 'two_estimates'][m.group(1)] = round(
+                float(row['TotalDurationNs']) / float(row['Calls']) / 1e3, 2)
+    return out
+
+
+def sdr_bench(a, c, e, off, off_h, longest, fs):
+    """The device pass of the BSS-eval SDR with one and with two estimates beside the STOI pass, and the host function on the
+    same set."""
+    n, K = a.recordings, metrics.SDR_FILTER_LENGTH
+    spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
+    e2 = (c + 0.5 * (e - c)).contiguous()                     # a second estimate: the same noise 6 dB down
+    methods = (('stoi_ragged_call', lambda: metrics.stoi_ragged(c, e, off, fs, longest=longest)),
+               ('sdr_ragged_call', lambda: metrics.sdr_ragged(c, e, off)),
+               ('sdr_ragged_two_estimates_call', lambda: metrics.sdr_ragged(c, e, off, estimate2=e2)))
+    first = {}
+    for name, fn in methods:
+        first[name] = fn()
+        torch.cuda.synchronize()
+    times = timed_rounds(methods, a.min_seconds)
+    ch, eh = c.cpu().numpy(), e.cpu().numpy()
+    t0 = time.perf_counter()
+    host = np.array([metrics.sdr(ch[p:q], eh[p:q]) for p, q in spans])
+    host_s = time.perf_counter() - t0
+    total = int(off_h[-1])
+    res = {'metric': 'sdr_recordings', 'device': torch.cuda.get_device_name(0), 'recordings': n,
+           'audio_seconds': round(total / fs, 2), 'lengths_s': '1 .. 10 s at 16 kHz, uniform, seeded', 'filter_length': K,
+           'chunk': ops.SDR_CHUNK, 'chunks': int(sum(-(-(q - p + K - 1) // ops.SDR_CHUNK) for p, q in spans)),
+           'first_measurement': 'no earlier figure exists for this pass on the MI355X and nothing at the parent commit compares',
+           'timing': 'device events around one pass over the set; the three device methods alternate in 3 rounds, each filling a '
+                     'third of min_seconds with repeated passes; median over the passes.  host: wall clock of one loop of '
+                     'metrics.sdr over the set (numpy, fp64), signals already on the host',
+           'min_seconds': a.min_seconds,
+           'kernel_launches': {'sdr_ragged_call': ops.SDR_LAUNCHES, 'sdr_ragged_two_estimates_call': ops.SDR_LAUNCHES,
+                               'stoi_ragged_call': 2 * 2 + 4, 'stoi_ragged_call_fills': 2},
+           'workspace_bytes': int(ops.sdr_workspace_bytes(n, total, K)), 'host_loop_s': round(host_s, 4)}
+    for name, _ in methods:
+        res[name] = pass_stats(times[name], n)
+    one, two = res['sdr_ragged_call']['ms_per_pass_median'], res['sdr_ragged_two_estimates_call']['ms_per_pass_median']
+    res['sdr_over_stoi_pass'] = round(one / res['stoi_ragged_call']['ms_per_pass_median'], 3)
+    res['two_estimates_over_two_calls'] = round(two / (2 * one), 3)
+    res['host_loop_over_device_pass'] = round(host_s * 1e3 / one, 1)
+    # operations from the shapes: the issue's count of the algorithm (5 K L multiply-adds per recording and estimate), and the
+    # multiply-adds the direct form here performs (R, D and the projection: 3 K L; 5 K L with two estimates)
+    res['flops'] = {'algorithmic_fp64_flop_one_estimate': 2 * 5 * K * total, 'direct_form_fp64_flop_one_estimate': 2 * 3 * K * total,
+                    'direct_form_fp64_flop_two_estimates': 2 * 5 * K * total, 'fp64_vector_peak_flops': FP64_VECTOR_PEAK,
+                    'peak_source': 'half the FP32 vector peak of the MI355X guide (157.3 TFLOPS); the guide lists no fp64 figure',
+                    'algorithmic_share_of_peak_whole_pass': round(2 * 5 * K * total / (one * 1e-3) / FP64_VECTOR_PEAK, 4),
+                    'direct_form_share_of_peak_whole_pass': round(2 * 3 * K * total / (one * 1e-3) / FP64_VECTOR_PEAK, 4),
+                    'direct_form_share_of_peak_whole_pass_two_estimates':
+                        round(2 * 5 * K * total / (two * 1e-3) / FP64_VECTOR_PEAK, 4),
+                    'note': 'whole-pass rates over peak (launch gaps and the serial solve included), not a kernel\'s share of peak'}
+    got = first['sdr_ragged_call'].cpu().numpy().astype(np.float64)
+    res['sdr_max_abs_diff_vs_host'] = float(np.nanmax(np.abs(got - host)))
+    res['second_estimate_equals_its_own_call'] = bool(torch.equal(first['sdr_ragged_two_estimates_call'][0], first['sdr_ragged_call']))
+    res['differences'] = ('this set (harmonic signals, a broadband part 30 dB down) is far worse conditioned than the set of '
+                          'tests/test_sdr_device.py; the difference above is not to be read against profiles/sdr_parity.json')
+    if a.kernel_stats:
+        res['kernel_us_rocprofv3'] = sdr_kernel_times(a.kernel_stats)
+        for tag, k in res['kernel_us_rocprofv3'].items():
+            if len(k) == 4:
+                res[f'solve_share_of_kernel_time_{tag}'] = round(k['solve'] / sum(k.values()), 3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None, help='default: profiles/score_bench.json (--frame-measures: '
                                                 'profiles/frame_measures_bench.json, --spectral-measures: '
-                                                'profiles/spectral_measures_bench.json); - for none')
+                                                'profiles/spectral_measures_bench.json, --sdr: profiles/sdr_bench.json); - for none')
+    ap.add_argument('--sdr', action='store_true',
+                    help='time metrics.sdr_ragged (one and two estimates) beside the STOI pass and the host function instead')
+    ap.add_argument('--kernel-stats', default=None, help='--sdr: a rocprofv3 kernel-stats CSV of a run of this tool')
     ap.add_argument('--frame-measures', action='store_true',
                     help='time metrics.frame_measures_ragged beside the STOI pass and the host function instead')
     ap.add_argument('--spectral-measures', action='store_true',
@@ -185,7 +273,8 @@ def main():
     ap.add_argument('--parent-json', default=None, help="this tool's JSON of the parent commit, same box, same session")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'spectral_measures_bench.json' if a.spectral_measures else
+        a.out = os.path.join(ROOT, 'profiles', 'sdr_bench.json' if a.sdr else
+                             'spectral_measures_bench.json' if a.spectral_measures else
                              'frame_measures_bench.json' if a.frame_measures else 'score_bench.json')
     dev = torch.device('cuda:0')
     fs = 16000
@@ -197,6 +286,8 @@ def main():
     off = torch.from_numpy(off_h).to(dev)
     longest = int(np.diff(off_h).max())
     spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
+    if a.sdr:
+        return write_result(sdr_bench(a, c, e, off, off_h, longest, fs), a.out)
     if a.spectral_measures:
         return write_result(spectral_measures_bench(a, c, e, off, off_h, longest, fs), a.out)
     if a.frame_measures:
