@@ -27,46 +27,6 @@
 #include <type_traits>
 #include <cstdlib>
 
-#ifndef DCS_X6_GU16
-#define DCS_X6_GU16 4
-#endif
-#ifndef DCS_EXP_LOOP
-#define DCS_EXP_LOOP 0      // timing probes of the tap loop (wrong results): 1 no A reads, 2 no B loads, 4 no gather after chunk 0
-#endif
-#ifndef DCS_MFMA_GATHER_PREFETCH
-#define DCS_MFMA_GATHER_PREFETCH 0      // measured: gather phases of a workgroup halve, its MFMA phases stretch by as much (r04 phase stamps)
-#endif
-#ifndef DCS_MFMA_PROGRESS_PRIO
-#define DCS_MFMA_PROGRESS_PRIO 0      // measured: the two workgroups of a CU finish 7 % apart instead of 25 %, the kernel lasts exactly as long (work-conserving)
-#endif
-#ifndef DCS_MFMA_STAGGER
-#define DCS_MFMA_STAGGER 0
-#endif
-#ifndef DCS_MFMA_COPY_AT_TOP
-#define DCS_MFMA_COPY_AT_TOP 1
-#endif
-#ifndef DCS_MFMA_LDS_BARRIER
-#define DCS_MFMA_LDS_BARRIER 1
-#endif
-#ifndef DCS_MFMA_XCD_REMAP
-#define DCS_MFMA_XCD_REMAP 1
-#endif
-#ifndef DCS_MFMA_SCALAR_B
-#define DCS_MFMA_SCALAR_B 1
-#endif
-#ifndef DCS_MFMA_PINGPONG
-#define DCS_MFMA_PINGPONG 1
-#endif
-#ifndef DCS_MFMA_EARLY_OPERANDS
-#define DCS_MFMA_EARLY_OPERANDS 3
-#endif
-#ifndef DCS_EXP_M16
-#define DCS_EXP_M16 0       // timing probes of the 16-column kernel (wrong results): 1 no stores, 2 no MFMA loop, 4 no gather, 8 return behind the table
-#endif
-#ifndef DCS_X6_GU32
-#define DCS_X6_GU32 8       // gather loads in flight per thread at 32-channel chunks of the emulated kernel
-#endif
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -128,7 +88,6 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
     // pixel tiles of one or two (column tile, class) pairs, i.e. ~1 MB of B that stays in its L2 and is shared by a CU's
     // workgroups in L1.  Speed only: any placement gives the same result.
     unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-#if DCS_MFMA_XCD_REMAP
     {
         const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
         const unsigned n = (bz * gy + by) * gx + bx, xcd = n & 7u, idx = n >> 3, q = total >> 3, r = total & 7u;
@@ -137,13 +96,7 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
         bx = __builtin_amdgcn_readfirstlane(L % gx);
         by = __builtin_amdgcn_readfirstlane((L / gx) % gy);
         bz = __builtin_amdgcn_readfirstlane(L / (gx * gy));
-#if DCS_MFMA_STAGGER
-        // experiment: the workgroup in a CU's second slot (hardware ids 256 .. 511, 768 .. ) starts ~one gather late, so that the
-        // two co-resident workgroups alternate gather and MFMA phases instead of running them in lockstep
-        if ((n >> 8) & 1u) __builtin_amdgcn_s_sleep(DCS_MFMA_STAGGER);
-#endif
     }
-#endif
     const conv::Cls& k = m.cls[bz];
     // pixels per workgroup = (4 / (WAVES_N WK)) * WM * 32 = TH * TW
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -188,7 +141,7 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
     const int kgo = TSP ? 0 : wk * U;                                  // ... first k-group
     int kgo_s = __builtin_amdgcn_readfirstlane(kgo);                   // (wave-uniform: the scalar copy for the B addresses;
     asm volatile("" : "+s"(kgo_s));                                    //  opaque, or the compiler sinks the readfirstlane below the multiplies)
-    const float* bbase = m.bm + k.bm_off + ((long)nt0 * 64 + lane) * 4;
+    const float* const bpanel = m.bm + k.bm_off;                       // this class's B panel
     const long b_tap_stride = (long)(BF ? m.KG / 2 : m.KG) * m.NT * 256, b_kg_stride = (long)m.NT * 256;
     const long b_plane_stride = (long)(k.kh * k.kw) * b_tap_stride;    // (PR = 2: planes of this class's panel)
 
@@ -213,12 +166,10 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
     // vg: k-group index inside an iteration = (tap offset vg / U, k-group vg % U)
     // (INPLACE, below: uniform panel base in SGPRs + one 32-bit lane offset, so that the 147 loads of the unrolled rows
     // share one address register instead of a 64-bit VGPR pair each — 252 VGPRs before, one wave per SIMD)
-    const char* ubase = reinterpret_cast<const char*>(m.bm + k.bm_off) +
+    const char* ubase = reinterpret_cast<const char*>(bpanel) +
                         (size_t)__builtin_amdgcn_readfirstlane(nt0) * 1024;
     const unsigned lane_off = (unsigned)lane * 16u;
-    bool bprobe_first = true;
     auto bload = [&](float4 (*dst)[WN], int c, int tp, int vg) {
-        if ((DCS_EXP_LOOP & 2) && !bprobe_first) return;
         tp += vg / U;
         const int g = vg % U;
         if (tp >= ntaps) { tp = TSP ? t0 : tp - ntaps; ++c; }
@@ -233,39 +184,28 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
                     dst[pl][j] = *reinterpret_cast<const float4*>(ubase + so + (unsigned)((pl * b_plane_stride + j * 256) * 4) + lane_off);
             return;
         }
-#if DCS_MFMA_SCALAR_B
         // Round 4: the fragment address is wave-uniform up to the lane's 16 bytes, so it is kept on the SCALAR unit (uniform panel
         // base + scalar byte offset + one constant lane-offset VGPR).  As per-lane 64-bit pointer arithmetic every tap cost two
         // v_mad_u64_u32, two v_mul_lo_u32 and ~8 v_lshl_add_u64 (quarter-rate / 64-bit VALU: ~100 issue cycles per tap per wave,
         // in order with the wave's own MFMAs): the probe that removed the B loads gained 16 % of dec1's forward, most of it this.
-        {
-            const long so = (tp * b_tap_stride + (long)(c * UALL + kgo_s + g) * b_kg_stride) * 4;     // scalar unit throughout
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-                for (int j = 0; j < WN; ++j) {
-                    typedef __attribute__((address_space(1))) const char gchar_t;       // (the asm would otherwise leave a flat pointer)
-                    typedef float f32x4n __attribute__((ext_vector_type(4)));
-                    typedef __attribute__((address_space(1))) const f32x4n gfloat4_t;
-                    gchar_t* sb = (gchar_t*)(ubase + (so + (pl * b_plane_stride + j * 256) * 4));
-                    unsigned lo = lane_off;
-                    asm volatile("" : "+s"(sb), "+v"(lo));             // SGPR pair + 32-bit lane offset in THIS block: global_load v, v_lo, s[base]
-                    dst[pl][j] = __builtin_bit_cast(float4, *(gfloat4_t*)(sb + lo));
-                }
-            return;
-        }
-#endif
-        const float* bp = bbase + tp * b_tap_stride + (long)(c * UALL + kgo + g) * b_kg_stride;
+        const long so = (tp * b_tap_stride + (long)(c * UALL + kgo_s + g) * b_kg_stride) * 4;     // scalar unit throughout
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
-            for (int j = 0; j < WN; ++j) dst[pl][j] = *reinterpret_cast<const float4*>(bp + pl * b_plane_stride + j * 256);
+            for (int j = 0; j < WN; ++j) {
+                typedef __attribute__((address_space(1))) const char gchar_t;       // (the asm would otherwise leave a flat pointer)
+                typedef float f32x4n __attribute__((ext_vector_type(4)));
+                typedef __attribute__((address_space(1))) const f32x4n gfloat4_t;
+                gchar_t* sb = (gchar_t*)(ubase + (so + (pl * b_plane_stride + j * 256) * 4));
+                unsigned lo = lane_off;
+                asm volatile("" : "+s"(sb), "+v"(lo));             // SGPR pair + 32-bit lane offset in THIS block: global_load v, v_lo, s[base]
+                dst[pl][j] = __builtin_bit_cast(float4, *(gfloat4_t*)(sb + lo));
+            }
     };
-    // B fragments of one whole tap (U k-groups) live in registers; the NEXT tap's are fetched during the first half of
-    // this tap's k-groups (two per group) into a second set and moved over at the end of the tap.  The compiler drains
+    // B fragments of one whole tap (U k-groups) live in registers; the NEXT tap's are fetched during this tap's k-groups
+    // (each group requests its own slot) into a second set and moved over at the top of the next tap.  The compiler drains
     // vmcnt to zero at every loop header (it cannot carry partial counts across the back edge): with the loads at the
-    // front of the body that drain finds them >= U/2 groups (>= 512 MFMA cycles) old instead of just issued.
-    constexpr int LPG = VU >= 2 ? 2 : 1;
+    // front of the body that drain finds them old instead of just issued.
     // INPLACE (the emulated 7x7 layer, enc1: PR = 2, a kernel ROW of 7 taps per iteration, one k-group per tap): three
     // planes x 7 taps of B fragments are 84 VGPRs, so there is ONE set; a slot is refilled right after its MFMAs with the
     // same tap of the next kernel row (7 k-groups = 1344 MFMA cycles ahead), and the row loop is fully unrolled (49 taps:
@@ -274,20 +214,10 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
     constexpr bool INPLACE = PR == 2 && TPI > 1;
     constexpr int NTAPS_C = INPLACE ? TPI * TPI : 0;
     float4 bcur[VU][NP][WN], bnxt[INPLACE ? 1 : VU][NP][WN];
-    constexpr bool PP = DCS_MFMA_PINGPONG && !INPLACE && DCS_MFMA_COPY_AT_TOP && DCS_MFMA_EARLY_OPERANDS == 3 && DCS_EXP_LOOP == 0 &&
-                        !DCS_MFMA_GATHER_PREFETCH && WM * WN < 4;         // (2 x 2 tiles per wave: the two bodies spill)
+    constexpr bool PP = !INPLACE && WM * WN < 4;                       // (2 x 2 tiles per wave: the two bodies spill)
     float4 bs2[PP ? 2 : 1][PP ? VU : 1][NP][WN];                      // PP: the two B-fragment sets (tap_body, below)
 #pragma unroll
-    for (int g = 0; g < VU; ++g) bload(PP ? bs2[0][PP ? g : 0] : (DCS_MFMA_COPY_AT_TOP && !INPLACE ? bnxt[INPLACE ? 0 : g] : bcur[g]), c_begin, t0, g);
-    if (DCS_EXP_LOOP & 2) {
-#pragma unroll
-        for (int g = 0; g < (INPLACE || DCS_MFMA_COPY_AT_TOP ? 0 : VU); ++g)
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-                for (int j = 0; j < WN; ++j) bnxt[g][pl][j] = bcur[g][pl][j];
-        bprobe_first = false;
-    }
+    for (int g = 0; g < VU; ++g) bload(PP ? bs2[0][PP ? g : 0] : (!INPLACE ? bnxt[INPLACE ? 0 : g] : bcur[g]), c_begin, t0, g);
 
     // source pixel of every patch pixel, as the element offset of its channel 0 in x1 (spx) and in x2 (spx2) — or -1 for a
     // zero (padding / inserted zero): the same for all channel chunks.  (Round 4: premultiplied by the channel counts here,
@@ -309,7 +239,8 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
     // pixel of every patch pixel comes from the table built once above: per slot a shift, an LDS read and one
     // 64-bit multiply-add (the index arithmetic it replaces — four runtime divisions per slot and chunk — kept the
     // VALU busy for ~30 % of a workgroup's life while its MFMA pipe idled).
-    constexpr int GU = (PR == 2 && CH == 32) ? DCS_X6_GU32 : (PR == 2 ? DCS_X6_GU16 : 4);
+    constexpr int X6_GU32 = 8, X6_GU16 = 4;                            // gather loads in flight per thread of the emulated kernel, at 32- / 16-channel chunks
+    constexpr int GU = (PR == 2 && CH == 32) ? X6_GU32 : (PR == 2 ? X6_GU16 : 4);
 #if DCS_ACT_IS_BF16
     typedef uint2 raw_t;                                               // two complex values = 4 bf16, as stored
 #else
@@ -372,14 +303,6 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
 #else
             float4 r = make_float4(__uint_as_float(__float_as_uint(v[u].x) & keep), __uint_as_float(__float_as_uint(v[u].y) & keep),
                                    __uint_as_float(__float_as_uint(v[u].z) & keep), __uint_as_float(__float_as_uint(v[u].w) & keep));
-#if defined(DCS_EXP_GATHER) && DCS_EXP_GATHER == 1
-            if (PR == 2) {     // timing probe (wrong results): the loaded bits stored as they are — the gather without the split
-                *(lds_f2*)dst = nf2{r.x, r.y};
-                *(lds_f2*)(dst + CH) = nf2{r.z, r.w};
-                *(lds_f2*)(dst + 2 * CH) = nf2{r.x, r.w};
-                continue;
-            }
-#endif
             if (PR == 2) {                                             // 2 complex -> 3 planes of 4 bf16 (exact split)
                 nu2 h0, h1, h2;
                 h0.x = dcs_split_pair(r.x, r.y); h0.y = dcs_split_pair(r.z, r.w);
@@ -396,17 +319,10 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
 #endif
         }
     };
-    // Round 4: the FIRST round of the next chunk's gather is requested during the LAST tap of this chunk's MFMA loop (behind
-    // that tap's B-fragment requests: vmcnt retires in order, and nothing in the rest of the tap waits on vector memory), so
-    // its memory round trip — the gather is latency-bound: a table read, a load the previous kernel's write-back has pushed
-    // out of L2, then the stores — runs under ~24 MFMAs and the chunk barrier instead of after them.  One round = GU slots per
-    // thread = the whole patch for the tiles of the train shapes.
-    // (32-channel chunks only: their launches hold two workgroups per CU whatever the register count; the GU x 4 held registers
-    // would cost the 16-channel instances their third wave per SIMD)
-    constexpr bool PREFETCH = DCS_MFMA_GATHER_PREFETCH != 0 && CH == 32 && PR == 2 && !INPLACE;
-    int o_pre[GU], pp_pre[GU];
-    raw_t v_pre[GU];
-    bool have_pre = false;
+    // (Measured and dropped, Round 4: the FIRST round of the next chunk's gather requested during the LAST tap of this chunk's
+    // MFMA loop, behind that tap's B-fragment requests, and stored after the chunk barrier.  The gather phases of a workgroup
+    // halved and its MFMA phases stretched by as much (round 4's phase stamps); per layer with and without it:
+    // profiles/r04_conv_probes.txt.)
     // (Measured and dropped: the first round of the NEXT chunk loaded into registers before this chunk's MFMA loop and stored
     // after it — +37 VGPRs take the 32-channel instances from three waves per SIMD to two and the first B-fragment wait of
     // the loop then also waits for the older patch loads: train step 3.950 -> 3.996 ms, inference 3.22 -> 3.37 ms.)
@@ -414,43 +330,24 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
     // drains vmcnt: the B fragments of the next chunk's first tap, requested during the last tap of this chunk, were waited for
     // right there — one exposed L2 round trip per chunk (dec1: 8 chunks; the probe without B loads ran 16 % faster, and neither
     // earlier requests, scalar addressing nor an XCD-local tile order recovered any of it).  Now they fly under the gather.
-#if DCS_MFMA_LDS_BARRIER
 #define DCS_CHUNK_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#else
-#define DCS_CHUNK_BARRIER() __syncthreads()
-#endif
-    // Progress-based wave priority (Round 4).  Phase stamps per workgroup (tools/fwd_diag.py, DCS_FDIAG_DUMP) showed the two
-    // co-resident workgroups of a CU finishing 25 % apart — dec1: 108 k cycles for the one dispatched first, 135 k for the
-    // second: the SIMD arbitrates issue by priority, then AGE, so the older workgroup's waves run nearly unimpeded, the younger
-    // one gets the leftover slots and then runs its last quarter alone on a pipe one wave per SIMD cannot fill; the kernel
-    // lasts as long as the slower one.  A workgroup now lowers its priority as it progresses through its (chunk, tap)
-    // iterations (3 -> 0 in quarters): whichever is ahead yields, both finish together.  (The weight-gradient kernel has done
-    // this per pixel tile since round 2.)
-#if DCS_MFMA_PROGRESS_PRIO
-    const int prio_total = (n_chunks - c_begin) * ((ntaps - t0 + TSTEP - 1) / TSTEP);
-    const int prio_q1 = prio_total / 4, prio_q2 = prio_total / 2, prio_q3 = prio_total - prio_total / 4;
-    int prio_it = 0;
-    __builtin_amdgcn_s_setprio(3);
-#endif
+    // Progress-based wave priority (Round 4, measured and dropped).  Phase stamps per workgroup (tools/fwd_diag.py,
+    // DCS_FDIAG_DUMP) showed the two co-resident workgroups of a CU finishing 25 % apart — dec1: 108 k cycles for the one
+    // dispatched first, 135 k for the second: the SIMD arbitrates issue by priority, then AGE, so the older workgroup's waves
+    // run nearly unimpeded, the younger one gets the leftover slots and then runs its last quarter alone on a pipe one wave per
+    // SIMD cannot fill; the kernel lasts as long as the slower one.  A variant in which a workgroup lowered its priority as it
+    // progressed through its (chunk, tap) iterations (3 -> 0 in quarters) brought the two to within 7 % of each other, and the
+    // kernel lasted exactly as long (the pipe is work-conserving), so it was not kept: profiles/r04_conv_probes.txt,
+    // profiles/r04_lone_wave.txt.  (The weight-gradient kernel did the same per pixel tile in round 2 and dropped it as well.)
     for (int ch = c_begin; ch < n_chunks; ++ch) {
         const long long g0 = FDIAG_NOW();
         DCS_CHUNK_BARRIER();                                           // previous chunk fully consumed
-#if (defined(DCS_EXP_GATHER) && DCS_EXP_GATHER == 2) || (DCS_EXP_LOOP & 4)
-        // timing probe (wrong results): no gather at all after the first chunk — what a perfectly hidden gather would leave
-        if (ch == c_begin)
-#endif
-        {
-            int pb = tp0;
-            if (PREFETCH && have_pre) {
-                gfinish(o_pre, pp_pre, v_pre);
-                pb += PPR * GU;
-            }
-            for (; pb < npatch; pb += PPR * GU) {
-                int o[GU], pp[GU];
-                raw_t v[GU];
-                gissue(ch, pb, o, pp, v);
-                gfinish(o, pp, v);
-            }
+        int pb = tp0;                                                  // (as the for statement's own variable: another block layout at the tap loop's entry)
+        for (; pb < npatch; pb += PPR * GU) {
+            int o[GU], pp[GU];
+            raw_t v[GU];
+            gissue(ch, pb, o, pp, v);
+            gfinish(o, pp, v);
         }
         DCS_CHUNK_BARRIER();
         const long long g1 = FDIAG_NOW();
@@ -477,25 +374,15 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
         // receives the next tap's fragments, k-group by k-group, and the roles swap with the tap — no hand-over copy
         // (VU x NP x WN x 4 moves per tap and wave), and a k-group's fragments are waited for where THAT k-group starts, a
         // whole tap after their request; the copy at the top of a tap waited for all of them at once, i.e. also for the ones
-        // requested one k-group earlier (the removal probe DCS_EXP_LOOP & 8: dec1 72 -> 64 us).
+        // requested one k-group earlier (a probe that skipped the hand-over: dec1 72 -> 64 us, profiles/r04_conv_probes.txt).
         auto tap_body = [&](auto parc, int tap) {
             constexpr int P = decltype(parc)::value;
             float4 (*const cur_)[NP][WN] = PP ? bs2[P] : bcur;
             float4 (*const nxt_)[NP][WN] = PP ? bs2[P ^ 1] : bnxt;
-#if DCS_MFMA_PROGRESS_PRIO
-            if (prio_it == prio_q1) __builtin_amdgcn_s_setprio(2);
-            else if (prio_it == prio_q2) __builtin_amdgcn_s_setprio(1);
-            else if (prio_it == prio_q3) __builtin_amdgcn_s_setprio(0);
-            ++prio_it;
-#endif
-#if DCS_MFMA_COPY_AT_TOP
             // Round 4: the prefetched set moves over at the TOP of a tap, not at its end.  At the end, the last tap of a chunk
             // waited (vmcnt) for the next chunk's first fragments — requested half a tap earlier — BEFORE the gather: one exposed
             // L2 round trip per chunk.  Now that request flies under the gather's two barriers and its own memory round trip.
-            // (DCS_EXP_LOOP & 8: timing probe, wrong results — the hand-over is skipped behind an opaque test, the loads stay)
-            bool do_copy = true;
-            if (DCS_EXP_LOOP & 8) { int z = m.KG; asm volatile("" : "+s"(z)); do_copy = z < 0; }
-            if (!INPLACE && !PP && do_copy) {
+            if (!INPLACE && !PP) {
 #pragma unroll
                 for (int g = 0; g < VU; ++g)
 #pragma unroll
@@ -503,7 +390,6 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
 #pragma unroll
                         for (int j = 0; j < WN; ++j) cur_[g][pl][j] = nxt_[INPLACE ? 0 : g][pl][j];
             }
-#endif
             const int tap2 = tap + TSTEP < ntaps ? tap + TSTEP : tap;  // clamped: the last prefetch re-reads this tap
             const int tapq2 = (tap2 / k.kw) * cols + (tap2 % k.kw);
             const int tapoff = tapq * PIX, tapoff2 = tapq2 * PIX;
@@ -516,26 +402,16 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
                     for (int i = 0; i < WM; ++i) {
                         const int aoff = pixoff[i] + pl * CH + (g + 1 < VU ? tapoff + ((g + 1) / U) * PIX + ((g + 1) % U) * 8 : tapoff2);
                         if constexpr (BF) {
-                            if (DCS_EXP_LOOP & 1) { afb[(g + 1) & 1][pl][i] = afb[g & 1][pl][i]; continue; }
                             afb[(g + 1) & 1][pl][i] = *(lds_bf8_t*)((lds_cf_t*)patch + aoff);
                         } else {
-                            if (DCS_EXP_LOOP & 1) { af[(g + 1) & 1][pl][i] = af[g & 1][pl][i]; continue; }
                             af[(g + 1) & 1][pl][i] = *reinterpret_cast<const float4*>(patch + aoff);
                         }
                     }
-#if DCS_MFMA_EARLY_OPERANDS
                 // Round 4: both operand streams are issued AHEAD of this k-group's MFMAs.  Left to the scheduler the LDS reads of
                 // the next k-group sank to just before this group's last MFMA (one MFMA = 32 cycles of cover for a ~100-cycle LDS
                 // round trip, every k-group), and the next tap's B fragments were requested after the first k-group's MFMAs, i.e.
                 // U - 1 k-groups before the copy that waits for them (one k-group, ~400 cycles, on the two-wave K-split tiles).
-                if (DCS_MFMA_EARLY_OPERANDS == 1 && !INPLACE && g * LPG < VU) {
-#pragma unroll
-                    for (int q = 0; q < LPG; ++q)
-                        if (g * LPG + q < VU) bload(nxt_[INPLACE ? 0 : g * LPG + q], ch, tap + TSTEP, g * LPG + q);
-                }
-                if (DCS_MFMA_EARLY_OPERANDS == 3 && !INPLACE) bload(nxt_[INPLACE ? 0 : g], ch, tap + TSTEP, g);   // this group's slot of the next tap
-                if (DCS_MFMA_EARLY_OPERANDS != 3) __builtin_amdgcn_sched_barrier(0);
-#endif
+                if (!INPLACE) bload(nxt_[INPLACE ? 0 : g], ch, tap + TSTEP, g);   // this group's slot of the next tap
                 // MFMAs straight from the ring slot ...
 #pragma unroll
                 for (int i = 0; i < WM; ++i)
@@ -559,10 +435,9 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[i][j], 0, 0, 0);
                         }
                     }
-#if DCS_MFMA_EARLY_OPERANDS == 3
-                // Mode 3: the next k-group's A reads and this group's share of the next tap's B loads are written AHEAD of the MFMAs
+                // The next k-group's A reads and this group's share of the next tap's B loads are written AHEAD of the MFMAs
                 // in the source (so each is requested a whole k-group / a whole tap before its use) and INTERLEAVED with them by the
-                // scheduler — one load behind each MFMA — instead of in one burst in front of them (mode 1: 6 LDS reads + 6 global
+                // scheduler — one load behind each MFMA — instead of in one burst in front of them (measured: 6 LDS reads + 6 global
                 // loads = ~120 issue cycles before the first MFMA of every k-group: a lone wave ran at 54 % of the pipe, 61 % as
                 // the compiler orders it by itself: profiles/r04_lone_wave.txt).
                 if (!INPLACE) {
@@ -576,29 +451,12 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
                     if (NM < NA) __builtin_amdgcn_sched_group_barrier(0x100, NA - NM, 0);
                     if (NM < NA + NB) __builtin_amdgcn_sched_group_barrier(0x020, NA + NB - (NM > NA ? NM : NA), 0);
                 }
-#endif
-                // next tap's fragments (scheduling barriers pin the loads here, ahead of the remaining MFMA groups)
+                // INPLACE: the slot's refill (scheduling barriers pin the loads here, ahead of the remaining MFMA groups)
                 __builtin_amdgcn_sched_barrier(0);
-                if (PREFETCH && g == 0 && tap + TSTEP >= ntaps && ch + 1 < n_chunks) {      // last tap of the chunk, behind its first MFMA group
-                    gissue(ch + 1, tp0, o_pre, pp_pre, v_pre);
-                    have_pre = true;
-                }
                 if (INPLACE) {
                     bload(cur_[g], ch, tap + TSTEP, g);
-                } else if (DCS_MFMA_EARLY_OPERANDS != 1 && DCS_MFMA_EARLY_OPERANDS != 3 && g * LPG < VU) {
-#pragma unroll
-                    for (int q = 0; q < LPG; ++q)
-                        if (g * LPG + q < VU) bload(nxt_[INPLACE ? 0 : g * LPG + q], ch, tap + TSTEP, g * LPG + q);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-            }
-            if (!INPLACE && !DCS_MFMA_COPY_AT_TOP) {
-#pragma unroll
-                for (int g = 0; g < VU; ++g)
-#pragma unroll
-                    for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-                        for (int j = 0; j < WN; ++j) cur_[g][pl][j] = nxt_[INPLACE ? 0 : g][pl][j];
             }
             if (VU & 1) {                                               // odd U (bf16, CH = 8): the prefetch landed in set 1
 #pragma unroll
@@ -636,9 +494,6 @@ __global__ __launch_bounds__(256) void cconv_mfma_kernel(MArgs m) {
         }
         d_mfma += FDIAG_NOW() - g1;
     }
-#if DCS_MFMA_PROGRESS_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     const long long d_epi = FDIAG_NOW();
 #ifdef DCS_FWD_DIAG
     auto diag_out = [&]() {
@@ -909,10 +764,9 @@ __global__ __launch_bounds__(256) void cconv_mfma16_kernel(MArgs m) {
     static_assert(256 % Q == 0, "a thread owns a fixed channel pair");
     const int tq = t % Q, tp0 = t / Q;
 
-    if (DCS_EXP_M16 & 8) { __syncthreads(); return; }
     for (int ch = 0; ch < n_chunks; ++ch) {
         __syncthreads();
-        if (!(DCS_EXP_M16 & 4)) {
+        {                                                              // the gather of chunk ch
             const int c = ch * CH + 2 * tq;
             const bool first = c < a.C1;
             const char* const xb = first ? reinterpret_cast<const char*>(a.x1) : reinterpret_cast<const char*>(a.x2);
@@ -1025,8 +879,8 @@ __global__ __launch_bounds__(256) void cconv_mfma16_kernel(MArgs m) {
                 }
             }
         };
-        if (!(DCS_EXP_M16 & 2)) run_class(std::integral_constant<int, 0>{});
-        if constexpr (NC > 1 && !(DCS_EXP_M16 & 2)) {
+        run_class(std::integral_constant<int, 0>{});
+        if constexpr (NC > 1) {
             if (n_cls > 1) run_class(std::integral_constant<int, 1>{});
             if (n_cls > 2) run_class(std::integral_constant<int, 2>{});
             if (n_cls > 3) run_class(std::integral_constant<int, 3>{});
@@ -1066,11 +920,7 @@ __global__ __launch_bounds__(256) void cconv_mfma16_kernel(MArgs m) {
                 }
                 float v = acc[cc][i][r] + bv;
                 v = conv::col_affine(a.coef, v, n, ca);
-#if DCS_EXP_M16 & 1
-                if (oy < k.Hc && ox < k.Wc && v == 123456.f)          // (timing probe: no output stores)
-#else
                 if (oy < k.Hc && ox < k.Wc)
-#endif
                     dcs_st1(yb + ((oy * m.os_f + k.oo_f) * a.Wout + ox * m.os_t + k.oo_t) * width + col, dcs_act(v, a.act));
             }
         if (stat_row) {
@@ -1172,9 +1022,6 @@ int launch_tpi(MArgs& m, long npix, hipStream_t stream) {
     size_t lds = (size_t)npix * ((PR == 2 ? 3 * CH + 4 : PR == 1 ? CH + 4 : 2 * CH + 4) + 2) * sizeof(float);   // patch + the two source-offset tables
     if (lds < 4 * 32 * 36 * sizeof(float)) lds = 4 * 32 * 36 * sizeof(float);        // the epilogue's four transpose tiles
     if (STAT && lds < (4 * 32 * 36 + 4 * WN * 80) * sizeof(float)) lds = (4 * 32 * 36 + 4 * WN * 80) * sizeof(float);   // + the statistics' combine area
-#ifdef DCS_FWD_ONE_PER_CU
-    if (lds < 84 * 1024) lds = 84 * 1024;                                            // experiment: one workgroup per CU
-#endif
     auto fn = cconv_mfma_kernel<WAVES_N, WM, WN, CH, PR, TPI, STAT, WK>;
     if (dcs_ensure_dynamic_lds((const void*)fn, lds) != hipSuccess) return DCS_ERR_LAUNCH;
     dim3 grid(a.tiles_w * a.tiles_h * a.B, (m.NT / (WAVES_N * WN)) * m.ksplit, m.ncls);

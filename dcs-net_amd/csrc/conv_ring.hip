@@ -30,19 +30,6 @@
 #include <cstdio>
 #include <cstdlib>
 
-#ifndef DCS_RING_PRIO_CONS
-#define DCS_RING_PRIO_CONS 3
-#endif
-#ifndef DCS_RING_PRIO_PROD
-#define DCS_RING_PRIO_PROD 3
-#endif
-#ifndef DCS_RING_ALT_ACC
-#define DCS_RING_ALT_ACC 0
-#endif
-#ifndef DCS_RING_EXP
-#define DCS_RING_EXP 0      // timing probes (wrong results): 1 no patch slices after the prologue, 2 no B requests after the prologue,
-#endif                      // 4 no fragment reads in the consumer loop, 8 no barriers in the loop, 16 no main loop at all
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -98,7 +85,6 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
         }
         return;
     }
-    if (DCS_RING_EXP & 32) return;                                     // (probe 32: the launch alone)
     const int vy0 = oy0 * a.sf - k.pad_f, vx0 = ox0 * a.st - k.pad_t;
     const int Cin = a.C1 + a.C2;
     const int kw = k.kw, ntaps = k.kh * k.kw;
@@ -106,7 +92,7 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
     const int npix = rows * cols;
     const int n_chunks = Cin / CH;
     const int SPC = ntaps / TPS;                                       // steps per chunk (>= 2: dcs_conv_ring_plan)
-    const int nsteps = (DCS_RING_EXP & 16) ? 0 : n_chunks * SPC;      // (probe 16: prologue + epilogue only)
+    const int nsteps = n_chunks * SPC;
     const int abytes = rp.abytes;
 
     // source pixel of every patch pixel as the BYTE offset of its channel 0 in x1 / x2, -1: a zero (conv_mfma.hip)
@@ -123,7 +109,6 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
         }
     }
     __syncthreads();
-    if (DCS_RING_EXP & 128) return;                                    // (probe 128: launch + table)
 
     // ---- the patch gather, shared by the prologue (all eight waves, chunk 0) and the producers' slices -----------------
     constexpr int SB = 16 / (int)sizeof(act2_t);                       // complex values per 16-byte source slot: 2 (fp32) / 4 (bf16)
@@ -150,12 +135,6 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
         float x = __uint_as_float(__float_as_uint(r.x) & keep), y = __uint_as_float(__float_as_uint(r.y) & keep);
         float z = __uint_as_float(__float_as_uint(r.z) & keep), w = __uint_as_float(__float_as_uint(r.w) & keep);
         nu2 h0, h1, h2;                                                // 2 complex -> 3 planes of 4 bf16 (exact split)
-        if (DCS_RING_EXP & 256) {                                      // (probe 256: the raw bits stored, no split)
-            *(lds_u2*)dst = nu2{__float_as_uint(x), __float_as_uint(y)};
-            *(lds_u2*)(dst + CH * 4) = nu2{__float_as_uint(z), __float_as_uint(w)};
-            *(lds_u2*)(dst + 2 * CH * 4) = nu2{__float_as_uint(x), __float_as_uint(w)};
-            return;
-        }
         h0.x = dcs_split_pair(x, y); h0.y = dcs_split_pair(z, w);
         h1.x = dcs_split_pair(x, y); h1.y = dcs_split_pair(z, w);
         h2.x = dcs_pack_bf16x2(x, y); h2.y = dcs_pack_bf16x2(z, w);
@@ -188,7 +167,6 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
         }
     }
 
-    if (DCS_RING_EXP & 64) return;                                     // (probe 64: launch + table + the first chunk's gather)
     f32x16 acc[WM];
 #pragma unroll
     for (int i = 0; i < WM; ++i)
@@ -199,7 +177,8 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
         // ============================================ producers ============================================
         // Every vector-memory instruction of a producer is hand-counted inline asm: hipcc waits vmcnt(0) for an ordinary load
         // beside an LDS-DMA in flight, which would drain the B requests of the steps ahead at every patch slice.
-        __builtin_amdgcn_s_setprio(DCS_RING_PRIO_PROD);
+        constexpr int PRIO_PROD = 3;                                   // wave priority of the producers, for the whole main loop
+        __builtin_amdgcn_s_setprio(PRIO_PROD);
         const int p = wave - 4, pt = p * 64 + lane;
         constexpr int PPR = 256 / Q;                                   // patch pixels per pass of the 256 producer lanes
         const int tq = pt % Q, tp0 = pt / Q;
@@ -262,7 +241,7 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
         // count never changes): two variants under a branch made the destination registers a phi, and hipcc placed the phi's copies
         // in front of the wait in one of the branches.
         auto a_wait = [&]() {
-            constexpr int CNT = (DCS_RING_EXP & 2) ? 0 : NBW;
+            constexpr int CNT = NBW;
             if constexpr (NA == 2) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(av[0]), "+v"(av[1]) : "n"(CNT) : "memory");
             else asm volatile("s_waitcnt vmcnt(%4)" : "+v"(av[0]), "+v"(av[1]), "+v"(av[2]), "+v"(av[3]) : "n"(CNT) : "memory");
         };
@@ -283,7 +262,7 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
         // (the loads are issued UNCONDITIONALLY — where no slice is due, of a valid address nobody uses — so that their
         // destination registers are defined in the trip that waits for them: a conditional definition makes them loop-carried
         // and hipcc copies loop-carried registers wherever it likes, also in front of the hand-written wait)
-        bool have = n_chunks > 1 && !(DCS_RING_EXP & 1);
+        bool have = n_chunks > 1;
         a_issue(n_chunks > 1 ? 1 : 0, tp0);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // chunk 0 stored; stages 0 .. D - 1 landed
         RING_BARRIER();                                                // B_0
@@ -294,11 +273,11 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
             // the slice step s + 1 writes: position (ncs, njs), chunk ncs + 1
             int ncs = cs, njs = js + 1;
             if (njs == SPC) { njs = 0; ++ncs; }
-            have = njs <= SPC - 2 && ncs + 1 < n_chunks && s + 1 < nsteps && !(DCS_RING_EXP & 1);
+            have = njs <= SPC - 2 && ncs + 1 < n_chunks && s + 1 < nsteps;
             a_issue(ncs + 1 < n_chunks ? ncs + 1 : n_chunks - 1, have ? tp0 + njs * slice : tp0);
-            if (!(DCS_RING_EXP & 2)) b_next();                         // stage s + D (or the last one again)
+            b_next();                                                  // stage s + D (or the last one again)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // the patch stores of the slice finished in the previous trip
-            if (!(DCS_RING_EXP & 8)) RING_BARRIER();                   // B_{s+1}
+            RING_BARRIER();                                            // B_{s+1}
             // behind the barrier: retire this trip's slice (its loads are older than the NBW requests behind them) — the wait
             // also retires every B stage requested in EARLIER trips (<= s - 1 + D >= s + 3), in front of the next barrier
             a_wait();
@@ -307,7 +286,8 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
         }
     } else {
         // ============================================ consumers ============================================
-        __builtin_amdgcn_s_setprio(DCS_RING_PRIO_CONS);
+        constexpr int PRIO_CONS = 3;                                   // ... and of the consumers
+        __builtin_amdgcn_s_setprio(PRIO_CONS);
         const int wm = wave >> 1, wn = wave & 1;
         const int kk = lane >> 5, li = lane & 31;
         unsigned apix[WM];                                             // byte offset of this lane's pixel (tap (0,0), k-group 0) in a patch buffer
@@ -346,22 +326,14 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
         for (int s = 0; s < nsteps; ++s) {
 #pragma unroll
             for (int it = 0; it < IPS; ++it) {
-                if (DCS_RING_EXP & 4) {
-                } else if (it + 1 < IPS) rd((it + 1) & 1, c_ab, c_tw, c_bs, it + 1);
+                if (it + 1 < IPS) rd((it + 1) & 1, c_ab, c_tw, c_bs, it + 1);
                 else rd((it + 1) & 1, n_ab, n_tw, n_bs, 0);
                 if (PR == 2) {                                          // a0 b2, a1 b1, a2 b0, a0 b1, a1 b0, a0 b0 (conv_mfma.hip's order)
                     constexpr int pa[6] = {0, 1, 2, 0, 1, 0}, pb[6] = {2, 1, 0, 1, 0, 0};
-#if DCS_RING_ALT_ACC
-#pragma unroll
-                    for (int e = 0; e < 6; ++e)                         // the two accumulators alternate (each keeps its own term order)
-#pragma unroll
-                        for (int i = 0; i < WM; ++i)
-#else
 #pragma unroll
                     for (int i = 0; i < WM; ++i)
 #pragma unroll
                         for (int e = 0; e < 6; ++e)
-#endif
                             acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[it & 1][pa[e] < NP ? pa[e] : 0][i],
                                                                              fb[it & 1][pb[e] < NP ? pb[e] : 0], acc[i], 0, 0, 0);
                 } else {
@@ -402,7 +374,7 @@ __global__ __launch_bounds__(512) void cconv_ring_kernel(MArgs m, RingP rp) {
             c_ab = n_ab; c_bs = n_bs;
 #pragma unroll
             for (int e = 0; e < TPS; ++e) c_tw[e] = n_tw[e];
-            if (!(DCS_RING_EXP & 8)) RING_BARRIER();                   // B_{s+1}
+            RING_BARRIER();                                            // B_{s+1}
         }
     }
     __builtin_amdgcn_s_setprio(0);

@@ -42,16 +42,6 @@ struct WArgs {
     const uint4* gy_planes;
 };
 
-#ifndef DCS_WG_SETPRIO
-#define DCS_WG_SETPRIO 0      // progress-based wave priority (3 -> 0 over a workgroup's tiles): off since the kernel runs as the
-                             // BACKGROUND of the backward pass (dcs_common.h, DCS_PRIO_CRITICAL); standalone it measured neutral
-#endif
-#ifndef DCS_WG_RING_BIG
-#define DCS_WG_RING_BIG 2
-#endif
-#ifndef DCS_WG_RING_SMALL
-#define DCS_WG_RING_SMALL 4
-#endif
 #ifdef DCS_WGRAD_DIAG
 #define WDIAG_NOW() ((long long)__builtin_amdgcn_s_memtime())
 long long* g_wdbg = nullptr;
@@ -132,24 +122,13 @@ void cconv_wgrad_mfma_kernel(WArgs w) {
 
     long long d_gather = 0, d_mfma = 0, d_tiles = 0;
     const long long d_start = WDIAG_NOW();
-    int tiles_done = 0;
-    const int my_tiles = (w.total_tiles - (int)blockIdx.x + w.n_slabs - 1) / w.n_slabs;      // >= 1: n_slabs <= total_tiles
-    for (int tl = blockIdx.x; tl < w.total_tiles; tl += w.n_slabs, ++tiles_done) {
+    for (int tl = blockIdx.x; tl < w.total_tiles; tl += w.n_slabs) {
         const long long s0 = WDIAG_NOW();
         // Co-resident workgroups do equal work; the SIMD's oldest-first arbitration lets the first one run ahead and the
-        // last one finish alone on a pipe one wave cannot fill (dec2, four per CU: lifetimes 76 / 95 / 111 / 124 us).  A
-        // workgroup that is ahead yields: its priority falls with the share of its tiles it has finished (100 - 118 us).
-        {
-            const int q = tiles_done * 4 / my_tiles;
-#if DCS_WG_SETPRIO
-            if (q == 0) __builtin_amdgcn_s_setprio(3);
-            else if (q == 1) __builtin_amdgcn_s_setprio(2);
-            else if (q == 2) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-#else
-            (void)q;
-#endif
-        }
+        // last one finish alone on a pipe one wave cannot fill (dec2, four per CU: lifetimes 76 / 95 / 111 / 124 us).  Round 2
+        // let a workgroup that is ahead yield — its priority fell (3 -> 0) with the share of its tiles it had finished: lifetimes
+        // 100 - 118 us.  Dropped since the kernel runs as the BACKGROUND of the backward pass (dcs_common.h, DCS_PRIO_CRITICAL);
+        // standalone it measured neutral.
         const int b = tl / tiles_per_img, tile_id = tl % tiles_per_img;
         const int oy0 = (tile_id / a.tiles_w) * w.TH, ox0 = (tile_id % a.tiles_w) * w.TW;
         const int vy0 = oy0 * a.sf - pad_f, vx0 = ox0 * a.st - pad_t;
@@ -355,21 +334,6 @@ void cconv_wgrad_mfma_kernel(WArgs w) {
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
-#ifndef DCS_X6_FASTMASK
-#define DCS_X6_FASTMASK 1
-#endif
-#ifndef DCS_X6_CFMAP
-#define DCS_X6_CFMAP 1
-#endif
-#ifndef DCS_X6_FASTLOAD
-#define DCS_X6_FASTLOAD 1
-#endif
-#ifndef DCS_X6_BPIPE
-#define DCS_X6_BPIPE 0       // reads of the next tap group ahead of the current MFMAs: +50 VGPRs, step +0.4 % (measured)
-#endif
-#ifndef DCS_X6_TAP_GROUP
-#define DCS_X6_TAP_GROUP 2
-#endif
 constexpr int PIXE = 28;       // LDS floats per patch pixel: 3 planes x 8 floats (16 bf16) + 4 floats of pad
 
 // TS (the 7x7 layer with 16 output channels, as in the native kernel): the four waves split the TAPS (13 each) and every
@@ -405,8 +369,7 @@ __global__ __launch_bounds__(256, 2) void cconv_wgrad_x6_kernel(WArgs w) {
     // at a pitch of 96 bytes (stride 1: 96 n mod 256 runs through the multiples of 32) or 112 bytes (stride 2: 224 n).
     // So lane group lk = 2h + o holds, as k-indices 8 lk .. 8 lk + 7, the pixels 16h + 4o + {0..3} and 16h + 8 + 4o + {0..3}
     // of the k-step — for BOTH operands (with 8 consecutive pixels per group every read was 2-way conflicted at any pitch).
-    constexpr bool CF = DCS_X6_CFMAP;
-    const int PIXR = CF ? (a.st == 2 ? PIXE : 24) : PIXE;
+    const int PIXR = a.st == 2 ? PIXE : 24;
     // NP = 3: fp32 operands split into three bf16 planes, six MFMAs per product (the emulation).  NP = 1 (activations STORED in
     // bf16, dcs_common.h): the stored bits are the operands — plane 0 only, one MFMA per product, no split anywhere.
     constexpr int NP = DCS_ACT_IS_BF16 ? 1 : 3;
@@ -436,30 +399,17 @@ __global__ __launch_bounds__(256, 2) void cconv_wgrad_x6_kernel(WArgs w) {
     // byte offsets of this lane's 8 pixels of a k-step's first row(s) from the tile origin, row tile 0 (row tile i: + 64 i bytes)
     unsigned goff[8];
     {
-        const int p80 = DCS_X6_CFMAP ? 16 * (lk >> 1) + 4 * (lk & 1) : 8 * lk;
+        const int p80 = 16 * (lk >> 1) + 4 * (lk & 1);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int pp = p80 + (DCS_X6_CFMAP ? (e < 4 ? e : e + 4) : e);
+            const int pp = p80 + (e < 4 ? e : e + 4);
             goff[e] = (unsigned)((((pp >> w.twshift) * w.os_f * w.Wy + (pp & (w.TW - 1)) * w.os_t) * N1 + gcol[0]) * 4);
         }
     }
     long long d_gather = 0, d_mfma = 0, d_tiles = 0;
     const long long d_start = WDIAG_NOW();
-    int tiles_done = 0;
-    const int my_tiles = (w.total_tiles - (int)blockIdx.x + w.n_slabs - 1) / w.n_slabs;
-    for (int tl = blockIdx.x; tl < w.total_tiles; tl += w.n_slabs, ++tiles_done) {
+    for (int tl = blockIdx.x; tl < w.total_tiles; tl += w.n_slabs) {
         const long long s0 = WDIAG_NOW();
-        {
-            const int q = tiles_done * 4 / my_tiles;
-#if DCS_WG_SETPRIO
-            if (q == 0) __builtin_amdgcn_s_setprio(3);
-            else if (q == 1) __builtin_amdgcn_s_setprio(2);
-            else if (q == 2) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-#else
-            (void)q;
-#endif
-        }
         const int b = tl / tiles_per_img, tile_id = tl % tiles_per_img;
         const int oy0 = (tile_id / a.tiles_w) * w.TH, ox0 = (tile_id % a.tiles_w) * w.TW;
         const int vy0 = oy0 * a.sf - pad_f, vx0 = ox0 * a.st - pad_t;
@@ -539,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void cconv_wgrad_x6_kernel(WArgs w) {
         typedef __attribute__((address_space(1))) const float gfl_t;
         gch_t* gy_tile = (gch_t*)(gyb + ((long)(oy0 * w.os_f + oo_f) * w.Wy + ox0 * w.os_t + oo_t) * N1);
         auto load_g = [&](int ks, float (*dst)[8]) {
-            if (DCS_X6_FASTLOAD && !PA && !DCS_ACT_IS_BF16 && interior) {
+            if (!PA && !DCS_ACT_IS_BF16 && interior) {
                 int ksu = __builtin_amdgcn_readfirstlane(ks);
                 gch_t* sb = gy_tile + (long)((((ksu * 32) >> tws) * w.os_f * w.Wy + ((ksu * 32) & twm) * w.os_t) * N1) * 4;
                 asm volatile("" : "+s"(sb));
@@ -552,13 +502,13 @@ __global__ __launch_bounds__(256, 2) void cconv_wgrad_x6_kernel(WArgs w) {
                 }
                 return;
             }
-            const int p8 = CF ? ks * 32 + 16 * (lk >> 1) + 4 * (lk & 1) : ks * 32 + 8 * lk;     // e < 4: pixels p8 + e; e >= 4: p8 + 8 + (e - 4)
+            const int p8 = ks * 32 + 16 * (lk >> 1) + 4 * (lk & 1);     // e < 4: pixels p8 + e; e >= 4: p8 + 8 + (e - 4)
             const int oy = oy0 + (p8 >> tws), oxb = ox0 + (p8 & twm);
             const bool rowok = oy < a.Hout;
             const int soff = ((oy * w.os_f + oo_f) * w.Wy + oxb * w.os_t + oo_t) * N1;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int ee = CF ? (e < 4 ? e : e + 4) : e;
+                const int ee = e < 4 ? e : e + 4;
                 const int off = (rowok && oxb + ee < a.Wout) ? soff + ee * estr : 0;
 #pragma unroll
                 for (int i = 0; i < MT; ++i) dst[i][e] = dcs_ld1(gyb + off + gcl[i]);
@@ -570,7 +520,7 @@ __global__ __launch_bounds__(256, 2) void cconv_wgrad_x6_kernel(WArgs w) {
         for (int j = 0; j < 8 / WS; ++j) {                             // (tiles of up to 256 pixels: tile_shape_for)
             const int ks = part + j * WS;
             if (ks >= nks) break;
-            const int p8 = CF ? ks * 32 + 16 * (lk >> 1) + 4 * (lk & 1) : ks * 32 + 8 * lk;
+            const int p8 = ks * 32 + 16 * (lk >> 1) + 4 * (lk & 1);
             const int py = p8 >> tws, px0 = p8 & twm;
             const bool rowok = oy0 + py < a.Hout;
             // operand A: the three planes of this lane's 8 g_Y values per row tile
@@ -597,15 +547,15 @@ __global__ __launch_bounds__(256, 2) void cconv_wgrad_x6_kernel(WArgs w) {
                 float r[8];
                 // (interior tiles — wave-uniform test — skip the per-value masks; only the workgroups of the first input
                 // chunk need the bias sums: ~30 % of the k-step's VALU work beside its 72 MFMAs)
-                if (DCS_X6_FASTMASK && interior) {
+                if (interior) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) r[e] = raw[j & 1][i][e];
                 } else {
 #pragma unroll
                     for (int e = 0; e < 8; ++e)
-                        r[e] = (rowok && ox0 + px0 + (CF ? (e < 4 ? e : e + 4) : e) < a.Wout && colok[i]) ? raw[j & 1][i][e] : 0.f;
+                        r[e] = (rowok && ox0 + px0 + (e < 4 ? e : e + 4) < a.Wout && colok[i]) ? raw[j & 1][i][e] : 0.f;
                 }
-                if (!DCS_X6_FASTMASK || ci0 == 0) {
+                if (ci0 == 0) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) bsum[i] += r[e];
                 }
@@ -624,11 +574,12 @@ __global__ __launch_bounds__(256, 2) void cconv_wgrad_x6_kernel(WArgs w) {
             // operand B: lane (row q = li / 4, column quad li % 4) of its 16-lane group addresses pixel 8 lk + q (+ 4)
             const int q = li >> 2, p4 = li & 3;
             const int xrow0 = ((py * a.sf) * a.cols + (px0 + q) * a.st) * PIXR + p4 * 2;
-            const int xrow1 = xrow0 + (CF ? 8 : 4) * a.st * PIXR;
-            // TG taps at a time, terms outermost: consecutive MFMAs go to TG x MT different accumulators.  The transposed reads
-            // of tap group n + 1 are issued BEFORE the MFMAs of group n (two operand sets): issued right in front of their own
-            // MFMAs, every group waited out an LDS round trip (s_waitcnt lgkmcnt(0) after 12 reads, three times per k-step).
-            constexpr int TG = DCS_X6_TAP_GROUP;
+            const int xrow1 = xrow0 + 8 * a.st * PIXR;
+            // TG taps at a time, terms outermost: consecutive MFMAs go to TG x MT different accumulators.  A group's transposed
+            // reads are issued right in front of its own MFMAs, into alternating operand sets.  (Measured and dropped: the reads of
+            // tap group n + 1 issued BEFORE the MFMAs of group n, between scheduling barriers, to hide the LDS round trip every
+            // group waits out — +50 VGPRs, train step +0.4 %.)
+            constexpr int TG = 2;
             constexpr int NG = (TAPS + TG - 1) / TG;
             bf16x8w bp[2][TG][NP];
             auto read_group = [&](int gidx, bf16x8w (*dst)[NP]) {
@@ -646,12 +597,9 @@ __global__ __launch_bounds__(256, 2) void cconv_wgrad_x6_kernel(WArgs w) {
                     }
                 }
             };
-            if (DCS_X6_BPIPE) read_group(0, bp[0]);
 #pragma unroll
             for (int gi = 0; gi < NG; ++gi) {
-                if (!DCS_X6_BPIPE) read_group(gi, bp[gi & 1]);
-                else if (gi + 1 < NG) read_group(gi + 1, bp[(gi + 1) & 1]);
-                if (DCS_X6_BPIPE) __builtin_amdgcn_sched_barrier(0);
+                read_group(gi, bp[gi & 1]);
                 constexpr int pa[6] = {0, 1, 2, 0, 1, 0}, pb[6] = {2, 1, 0, 1, 0, 0};         // smallest terms first
 #pragma unroll
                 for (int e = (NP == 3 ? 0 : 5); e < 6; ++e)                                   // (NP = 1: the a0 b0 term alone)
@@ -663,7 +611,6 @@ __global__ __launch_bounds__(256, 2) void cconv_wgrad_x6_kernel(WArgs w) {
                                 f32x4& c = acc[i][gi * TG + u < TAPS ? gi * TG + u : 0];
                                 c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[i][pa[e] < NP ? pa[e] : 0], bp[gi & 1][u][pb[e] < NP ? pb[e] : 0], c, 0, 0, 0);
                             }
-                if (DCS_X6_BPIPE) __builtin_amdgcn_sched_barrier(0);
             }
         }
         d_mfma += WDIAG_NOW() - s1;
@@ -760,8 +707,7 @@ __global__ __launch_bounds__(256) void gy_planes_kernel(WArgs w, uint4* __restri
     const int b = tl / tiles_per_img, tile_id = tl % tiles_per_img;
     const int oy0 = (tile_id / a.tiles_w) * w.TH, ox0 = (tile_id % a.tiles_w) * w.TW;
     const int N1 = 2 * a.Cout, nblk = N1 >> 4;
-    constexpr bool CF = DCS_X6_CFMAP;
-    const int p8 = CF ? ks * 32 + 16 * (lk >> 1) + 4 * (lk & 1) : ks * 32 + 8 * lk;
+    const int p8 = ks * 32 + 16 * (lk >> 1) + 4 * (lk & 1);
     const int oy = oy0 + (p8 >> w.twshift), oxb = ox0 + (p8 & (w.TW - 1));
     const float* gyb = w.gy + (long)b * w.Hy * w.Wy * N1 + (mb * 16 + li);
     const long soff = ((long)(oy * w.os_f + w.oo_f[cls]) * w.Wy + oxb * w.os_t + w.oo_t[cls]) * N1;
@@ -769,7 +715,7 @@ __global__ __launch_bounds__(256) void gy_planes_kernel(WArgs w, uint4* __restri
     float r[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const int ee = CF ? (e < 4 ? e : e + 4) : e;
+        const int ee = e < 4 ? e : e + 4;
         r[e] = (oy < a.Hout && oxb + ee < a.Wout) ? gyb[soff + (long)ee * estr] : 0.f;
     }
     uint4* dst = out + ((((long)cls * w.total_tiles + tl) * nks + ks) * 3 * nblk + mb) * 64 + lane;
@@ -791,12 +737,9 @@ template <int KH_, int KW_, int MT_, int WS_, bool TS_ = false> struct Variant {
     static constexpr int GLW = TS_ ? MT_ : 4 / WS_;
 };
 
-#ifndef DCS_X6_MIN_TAPS
-#define DCS_X6_MIN_TAPS 0
-#endif
 // which emulated instance (cconv_wgrad_x6_kernel) stands in for a native variant, if any
 template <class V> struct X6 {
-    static constexpr bool ok = V::TS || ((V::WS == 1 || V::MT == 1) && V::KH * V::KW > DCS_X6_MIN_TAPS && V::KH < 7 && !(V::KH == 5 && V::WS == 4));
+    static constexpr bool ok = V::TS || ((V::WS == 1 || V::MT == 1) && V::KH < 7 && !(V::KH == 5 && V::WS == 4));
     static constexpr int MT = V::TS ? V::MT : (V::MT > 2 ? 2 : V::MT);
     static constexpr int WS = V::TS ? 1 : V::WS;
     static constexpr int CPB = V::TS ? V::MT * 8 : (4 / WS) * MT * 8;
