@@ -213,11 +213,17 @@ def stoi(x, y, fs_sig, extended=False):
 _device_tables = {}
 
 
-def stoi_band_edges(device):
-    """thirdoct(10000, 512, 15, 150)'s rows as bin ranges [lo, hi): int32 [2, 15] on `device` (cached)."""
-    key = ('bands', str(device))
+def _device_table(key, build):
+    """_device_tables[key], made by build() on the first call."""
     t = _device_tables.get(key)
     if t is None:
+        t = _device_tables[key] = build()
+    return t
+
+
+def stoi_band_edges(device):
+    """thirdoct(10000, 512, 15, 150)'s rows as bin ranges [lo, hi): int32 [2, 15] on `device` (cached)."""
+    def build():
         import torch
         obm, _ = thirdoct(FS, NFFT, NUMBAND, MINFREQ)
         lo, hi = [], []
@@ -228,23 +234,20 @@ def stoi_band_edges(device):
             assert len(nz) == b - a, 'thirdoct rows are contiguous bin ranges'
             lo.append(a)
             hi.append(b)
-        t = torch.tensor([lo, hi], dtype=torch.int32).to(device)
-        _device_tables[key] = t
-    return t
+        return torch.tensor([lo, hi], dtype=torch.int32).to(device)
+    return _device_table(('bands', str(device)), build)
 
 
 def resample_taps(fs_sig, device):
     """(h float32 [taps] on `device` = the normalised window of resample_oct(., FS, fs_sig), up, down) (cached)."""
     fs_sig = int(fs_sig)
-    key = ('taps', fs_sig, str(device))
-    t = _device_tables.get(key)
-    if t is None:
+
+    def build():
         import torch
         g = int(np.gcd(FS, fs_sig))
         h = _resample_window_oct(FS, fs_sig)
-        t = (torch.tensor(h / np.sum(h), dtype=torch.float32).to(device), FS // g, fs_sig // g)
-        _device_tables[key] = t
-    return t
+        return torch.tensor(h / np.sum(h), dtype=torch.float32).to(device), FS // g, fs_sig // g
+    return _device_table(('taps', fs_sig, str(device)), build)
 
 
 def _extended_result(out, extended):
@@ -466,13 +469,11 @@ def cepstrum_distance(x, y, fs):
 def measure_window(fs, device):
     """_measure_window(N) of rate fs as float64 [N] on `device` (cached): the host function's own bits."""
     N = frame_geometry(fs)[0]
-    key = ('measure_window', N, str(device))
-    t = _device_tables.get(key)
-    if t is None:
+
+    def build():
         import torch
-        t = torch.from_numpy(_measure_window(N)).to(device)
-        _device_tables[key] = t
-    return t
+        return torch.from_numpy(_measure_window(N)).to(device)
+    return _device_table(('measure_window', N, str(device)), build)
 
 
 def frame_measures_ragged(clean, estimate, offsets, fs, longest=None):
@@ -662,18 +663,16 @@ def spectral_tables(fs, device):
     band_weights float64, twiddles float64 [nfft, 2] = (cos, -sin)(2 pi m / nfft)); the window and the weights are the host
     function's own bits."""
     fs = int(fs)
-    key = ('spectral', fs, str(device))
-    t = _device_tables.get(key)
-    if t is None:
+
+    def build():
         import torch
         nfft = spectral_fft_size(fs)
         first, offset, weights = compact_bank(critical_band_bank(fs, nfft))
         angle = 2.0 * np.pi * np.arange(nfft) / nfft
         twiddles = np.stack([np.cos(angle), -np.sin(angle)], axis=1)
-        t = (measure_window(fs, device),) + tuple(torch.from_numpy(np.ascontiguousarray(v)).to(device)
-                                                  for v in (first, offset, weights, twiddles))
-        _device_tables[key] = t
-    return t
+        return (measure_window(fs, device),) + tuple(torch.from_numpy(np.ascontiguousarray(v)).to(device)
+                                                     for v in (first, offset, weights, twiddles))
+    return _device_table(('spectral', fs, str(device)), build)
 
 
 def spectral_measures_ragged(clean, estimate, offsets, fs, longest=None):

@@ -26,6 +26,7 @@ dropout_parity.json in $DCS_PARITY_DIR (default parity_out/); a full run's file 
 Not pinned here: DR-Net's dropout is ATen's (no replayable mask); bf16 activation storage with dropout is compared with the
 fp32 kernels only (tests/test_hip_bf16.py).
 """
+import functools
 import os
 import re
 import time
@@ -41,9 +42,10 @@ from oracle.cnet_oracle import C_NETWORK_Oracle, replay_dropout
 from oracle.nf_oracle import dcs_train_losses
 from oracle.seeded_state import fill_state, seeded_input
 
+from _ragged_helpers import record
 from test_dropout_cpu import miss, REL, ABS
 from test_layers_train_size import (BY_NAME, _bn_params, _check_block_with_ties, _cplx, _forward, _offset_input, _operands, _seed,
-                                    _sqrt2_covar, _record as _record_in)
+                                    _sqrt2_covar)
 
 pytestmark = pytest.mark.gpu
 
@@ -75,9 +77,7 @@ def seed_state(dev, value):
         ops.SEED_STATE = old
 
 
-def _record(path, value):
-    """Figures -> $DCS_PARITY_DIR/dropout_parity.json (default parity_out/ in the repository); path = nested keys."""
-    _record_in(path, value, name='dropout_parity.json')
+_record = functools.partial(record, 'dropout_parity.json')     # figures -> $DCS_PARITY_DIR/dropout_parity.json (default parity_out/)
 
 
 def _define(source, name):

@@ -17,6 +17,7 @@ from dcsnet import ops
 pytestmark = pytest.mark.gpu
 
 from oracle.seeded_state import fill_state, fill_state_stream   # noqa: E402
+from _ragged_helpers import flat                                 # noqa: E402
 
 
 @pytest.fixture(scope='module')
@@ -86,9 +87,8 @@ def _make_set(lengths, fs, seed, pause_fracs, snrs):
 
 def _flat(recs, dev):
     """-> (flat device buffer, int64 offsets on the device, the offsets on the host)."""
-    off = np.zeros(len(recs) + 1, dtype=np.int64)
-    np.cumsum([len(r) for r in recs], out=off[1:])
-    return torch.from_numpy(np.concatenate(recs)).to(dev), torch.from_numpy(off).to(dev), off
+    buf, off = flat(recs, dev)
+    return buf, off, off.cpu().numpy()
 
 
 def _host_e(clean, est, fs):

@@ -10,13 +10,9 @@ hinges on last bits (AR-shaped noise plus white noise satisfies it; pure tones w
 
 The largest observed differences go to frame_measures_parity.json in $DCS_PARITY_DIR (default parity_out/, kept out of git); a
 full run's file is committed as profiles/frame_measures_parity.json."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
-from scipy.signal import lfilter
 
 from dcsnet import _lib
 from dcsnet import metrics
@@ -25,8 +21,8 @@ from dcsnet import ops
 pytestmark = pytest.mark.gpu
 
 from oracle.seeded_state import fill_state   # noqa: E402
+from _ragged_helpers import ar_pair, check_against_host, flat, tied_pair   # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ('ssnr', 'llr', 'cd')
 LENGTHS_16K = (0, 1, 599, 600, 719, 720, 4800, 16000, 23457, 48007)      # 4800: the tied set; 23457: a 2000-sample zero head
 SNRS = (0, 10, 20)
@@ -38,21 +34,6 @@ def dev():
     assert torch.cuda.is_available(), 'GPU tests need a GPU'
     _lib.load()
     return torch.device('cuda:0')
-
-
-def _record(path, value):
-    """Figures -> $DCS_PARITY_DIR/frame_measures_parity.json (default parity_out/ in the repository): path = nested keys."""
-    out = os.path.join(os.environ.get('DCS_PARITY_DIR') or os.path.join(ROOT, 'parity_out'), 'frame_measures_parity.json')
-    try:
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        d = json.load(open(out)) if os.path.exists(out) else {}
-        node = d
-        for k in path[:-1]:
-            node = node.setdefault(k, {})
-        node[path[-1]] = value
-        json.dump(d, open(out, 'w'), indent=1, sort_keys=True)
-    except OSError:
-        pass
 
 
 # ---- signals -------------------------------------------------------------------------------------------------------------------
@@ -77,29 +58,11 @@ def _assert_input_condition(x, y, fs):
         silent = zero
 
 
-def _pair(L, snr_db, rng, zero_head=0):
-    """float32: AR(2)-shaped noise as the clean signal, white noise added at snr_db; zero_head samples of both are exactly 0."""
-    x = lfilter([1.0], [1.0, -1.6, 0.8], rng.standard_normal(L + 200))[200:]
-    v = rng.standard_normal(L)
-    if L:
-        v *= np.linalg.norm(x) / max(np.linalg.norm(v), 1e-30) * 10 ** (-snr_db / 20)
-    x, y = (0.1 * x).astype(np.float32), (0.1 * (x + v)).astype(np.float32)
-    x[:zero_head], y[:zero_head] = 0.0, 0.0
-    return x, y
-
-
-def _tied_pair(rng):
-    """4800 samples of period 120 (the hop at 16 kHz): every frame is the same frame, every value ties."""
-    x = np.tile(0.1 * rng.standard_normal(120), 40)
-    y = x + np.tile(0.03 * rng.standard_normal(120), 40)
-    return x.astype(np.float32), y.astype(np.float32)
-
-
 def _make_set(lengths, fs, seed):
     rng = np.random.default_rng(seed)
     clean, est = [], []
     for i, L in enumerate(lengths):
-        x, y = _tied_pair(rng) if L == 4800 else _pair(L, SNRS[i % 3], rng, zero_head=2000 if L == 23457 else 0)
+        x, y = tied_pair(rng) if L == 4800 else ar_pair(L, SNRS[i % 3], rng, zero_head=2000 if L == 23457 else 0)
         _assert_input_condition(x, y, fs)
         clean.append(x)
         est.append(y)
@@ -112,34 +75,14 @@ def set16():
     return _make_set(LENGTHS_16K, 16000, 31)
 
 
-def _flat(recs, dev):
-    off = np.zeros(len(recs) + 1, dtype=np.int64)
-    np.cumsum([len(r) for r in recs], out=off[1:])
-    flat = np.concatenate(recs) if off[-1] else np.zeros(0, np.float32)
-    return torch.from_numpy(flat.astype(np.float32)).to(dev), torch.from_numpy(off).to(dev)
-
-
 def _score(clean, est, fs, dev):
-    c, off = _flat(clean, dev)
-    e, _ = _flat(est, dev)
+    c, off = flat(clean, dev)
+    e, _ = flat(est, dev)
     return metrics.frame_measures_ragged(c, e, off, fs)
 
 
 def _check_against_host(got, host, what):
-    """2 float32 ulps of the host value + 1e-9; NaN exactly where the host has NaN.  Prints and records the largest difference."""
-    for k in KEYS:
-        g = got[k].cpu().numpy()
-        assert got[k].dtype == torch.float32 and g.shape == (len(host),)
-        h = np.array([m[k] for m in host])
-        assert np.array_equal(np.isnan(g), np.isnan(h)), (what, k, g, h)
-        ok = ~np.isnan(h)
-        diff = np.abs(g[ok].astype(np.float64) - h[ok])
-        tol = 2.0 * np.spacing(np.abs(h[ok]).astype(np.float32)).astype(np.float64) + 1e-9
-        worst = float(diff.max()) if ok.any() else 0.0
-        ratio = float((diff / tol).max()) if ok.any() else 0.0
-        print(f'[frame_measures] {what} {k}: max |device - host| = {worst:.3e}, {ratio:.3f} of the tolerance')
-        _record((what, k), {'max_abs_diff': worst, 'max_share_of_tolerance': ratio})
-        assert (diff <= tol).all(), (what, k, g, h)
+    check_against_host(got, host, KEYS, 'frame_measures', what, 'frame_measures_parity.json')
 
 
 # ---- 1. parity with the host contract ---------------------------------------------------------------------------------------
@@ -184,8 +127,8 @@ def test_graph_capture(dev, set16):
     """One linear stream capture of the call (no forks), replayed twice on new contents, equals the eager result bit for bit."""
     clean, est, _ = set16
     clean2, est2, _ = _make_set(LENGTHS_16K, 16000, 34)
-    c, off = _flat(clean, dev)
-    e, _ = _flat(est, dev)
+    c, off = flat(clean, dev)
+    e, _ = flat(est, dev)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
@@ -194,8 +137,8 @@ def test_graph_capture(dev, set16):
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         out = metrics.frame_measures_ragged(c, e, off, 16000)
-    c2, _ = _flat(clean2, dev)
-    e2, _ = _flat(est2, dev)
+    c2, _ = flat(clean2, dev)
+    e2, _ = flat(est2, dev)
     c.copy_(c2)
     e.copy_(e2)
     eager = metrics.frame_measures_ragged(c2, e2, off, 16000)
@@ -220,7 +163,7 @@ GUARD_F, GUARD_B = 12345.0, 0xA5
 def test_bad_offsets_stay_inside_the_buffers(dev, offsets):
     total, fs = 20000, 16000
     rng = np.random.default_rng(35)
-    x, y = _pair(total, 10, rng)
+    x, y = ar_pair(total, 10, rng)
     c, e = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
     off = torch.tensor(offsets, dtype=torch.int64, device=dev)
     n = len(offsets) - 1
@@ -289,7 +232,7 @@ def test_scorer_with_frame_measures(dev):
     net = fill_state(C_NETWORK(config, hp, 3), 3).to(dev).eval()
     enh = Enhancer(net, mode='dcs', segment_frames=T, overlap_frames=O, batch_segments=S, use_graph=False)
     rng = np.random.default_rng(41)
-    clean, noisy = zip(*(_pair(L, snr, rng) for L, snr in zip(SCORER_LENGTHS, (5, 0, 10, 15))))
+    clean, noisy = zip(*(ar_pair(L, snr, rng) for L, snr in zip(SCORER_LENGTHS, (5, 0, 10, 15))))
     clean, noisy = list(clean), list(noisy)
 
     plain = RecordingScorer(enh).score(noisy, clean, 16000)

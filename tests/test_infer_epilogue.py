@@ -36,7 +36,7 @@ bf16-storage rows equal; coefficient kernel 1.0e-7 .. 1.3e-7 (cpu32 6e-8 .. 1.7e
 2, 3, 4, 5, 7, 8, 10, K slices 8 / 8 on both P4 rows, and no plan line on the P6 / P7 rows.  No kernel fault was found: the
 copies without the scalar-FMA guard (splitk_reduce_kernel, cconv_direct_body) agree bit for bit with cbn_apply_kernel too.
 """
-import json
+import functools
 import os
 import re
 import subprocess
@@ -48,25 +48,14 @@ import torch
 from oracle import layer_fp64 as L64
 from oracle import rnet_layer_fp64 as R64
 import _plan_probe as P
+from _ragged_helpers import record
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = ('bf16x6', 'f32', 'bf16')
 LIVE = 0.2                     # share of the outputs each branch of an activation has to hold
 
 
-def _record(path, value):
-    """Figures -> $DCS_PARITY_DIR/infer_epilogue_parity.json (default parity_out/ in the repository): path = nested keys."""
-    out = os.path.join(os.environ.get('DCS_PARITY_DIR') or os.path.join(ROOT, 'parity_out'), 'infer_epilogue_parity.json')
-    try:
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        d = json.load(open(out)) if os.path.exists(out) else {}
-        node = d
-        for k in path[:-1]:
-            node = node.setdefault(k, {})
-        node[path[-1]] = value
-        json.dump(d, open(out, 'w'), indent=1, sort_keys=True)
-    except OSError:
-        pass
+_record = functools.partial(record, 'infer_epilogue_parity.json')     # figures -> $DCS_PARITY_DIR/infer_epilogue_parity.json (default parity_out/)
 
 
 def _compare(got, ref, ref32):

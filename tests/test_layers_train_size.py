@@ -39,9 +39,8 @@ out of git); a full run's file is committed as profiles/layer_parity.json.
 The comparator itself is tested without a GPU (the `not gpu` tests below): on real layer geometries at batch 2 it has to
 accept a second correct fp32 evaluation and reject each fault.
 """
-import json
+import functools
 import math
-import os
 import time
 
 import pytest
@@ -49,6 +48,7 @@ import torch
 
 from oracle import layer_fp64 as L64
 from oracle.layer_fp64 import ConvLayer
+from _ragged_helpers import record
 
 gpu = pytest.mark.gpu
 
@@ -321,22 +321,7 @@ def dev():
     torch.set_num_threads(threads)
 
 
-def _record(path, value, name='layer_parity.json'):
-    """Figures -> $DCS_PARITY_DIR/layer_parity.json, default parity_out/ in the repository (a full run's file is committed as
-    profiles/layer_parity.json): path = nested keys.  (The directory the two older _record helpers write to is named after
-    one particular job runner; this record goes where its caller says.)  name: another module's file in the same directory."""
-    out = os.path.join(os.environ.get('DCS_PARITY_DIR') or
-                       os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'parity_out'), name)
-    try:
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        d = json.load(open(out)) if os.path.exists(out) else {}
-        node = d
-        for k in path[:-1]:
-            node = node.setdefault(k, {})
-        node[path[-1]] = value
-        json.dump(d, open(out, 'w'), indent=1, sort_keys=True)
-    except OSError:
-        pass
+_record = functools.partial(record, 'layer_parity.json')     # figures -> $DCS_PARITY_DIR/layer_parity.json (default parity_out/)
 
 
 _WGRAD_REF = {}          # (layer, B) -> weight-gradient reference, absolute sums, e_cpu32, smallest fault (small tensors)

@@ -30,14 +30,14 @@ Measured (MI355X, full run, profiles/rnet_kernel_parity.json; DESIGN.md section 
 layer's error — conv forward 1.1e-6 / 1.1, data gradient 8.9e-7 / 2.0, weight + bias gradient 3.2e-7 / 2.0, BatchNorm
 6.3e-6 / 8.1 (5.4e-8 against 6.6e-9), LSTM 1.4e-6 / 3.0, enc0 / dec6 7.1e-7 / 1.4; the 16 x cpu32 fallback applied nowhere.
 """
-import json
-import os
+import functools
 import types
 
 import pytest
 import torch
 
 from oracle import rnet_layer_fp64 as R64
+from _ragged_helpers import record
 
 pytestmark = pytest.mark.gpu
 
@@ -52,20 +52,7 @@ def dev():
     torch.set_num_threads(threads)
 
 
-def _record(path, value):
-    """Figures -> $DCS_PARITY_DIR/rnet_kernel_parity.json (default parity_out/ in the repository): path = nested keys."""
-    out = os.path.join(os.environ.get('DCS_PARITY_DIR') or
-                       os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'parity_out'), 'rnet_kernel_parity.json')
-    try:
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        d = json.load(open(out)) if os.path.exists(out) else {}
-        node = d
-        for k in path[:-1]:
-            node = node.setdefault(k, {})
-        node[path[-1]] = value
-        json.dump(d, open(out, 'w'), indent=1, sort_keys=True)
-    except OSError:
-        pass
+_record = functools.partial(record, 'rnet_kernel_parity.json')     # figures -> $DCS_PARITY_DIR/rnet_kernel_parity.json (default parity_out/)
 
 
 def _judge(path, got, ref, ref32, **kw):

@@ -11,8 +11,7 @@ x2 of the one-sided spectrum, a shifted bin, a sign, the order of a - n) is O(1)
 against torch.fft.  Figures go to $DCS_PARITY_DIR/rstep_parity.json (default parity_out/, kept out of git); a full run's file
 is committed as profiles/rstep_parity.json.
 """
-import json
-import os
+import functools
 import sys
 import types
 import warnings
@@ -25,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle.nf_oracle import mag_phase_2_wave as mag_phase_2_wave_oracle   # noqa: E402
 from oracle.seeded_state import fill_state_stream, seeded_input            # noqa: E402
+from _ragged_helpers import record                                         # noqa: E402
 
 EPS = float(np.float32(10e-7))            # hparams['atan2_eps'] as the fp32 kernels and torch's fp32 add see it
 F_BINS = 256
@@ -38,19 +38,7 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _record(path, value):
-    out = os.path.join(os.environ.get('DCS_PARITY_DIR') or
-                       os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'parity_out'), 'rstep_parity.json')
-    try:
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        d = json.load(open(out)) if os.path.exists(out) else {}
-        node = d
-        for k in path[:-1]:
-            node = node.setdefault(k, {})
-        node[path[-1]] = value
-        json.dump(d, open(out, 'w'), indent=1, sort_keys=True)
-    except OSError:
-        pass
+_record = functools.partial(record, 'rstep_parity.json')     # figures -> $DCS_PARITY_DIR/rstep_parity.json (default parity_out/)
 
 
 # ------------------------------------------------------------------------------------------------------------ complex_abs

@@ -124,3 +124,33 @@ def test_evaluate_tool_help():
     r = subprocess.run([sys.executable, os.path.join(REPO, 'tools', 'evaluate.py'), '--help'], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert '--checkpoint' in r.stdout and 'noisy_dir' in r.stdout and '--csv' in r.stdout
+
+
+def test_the_measure_groups_table_orders_the_keys_and_signs_the_improvements():
+    """All 16 settings of the four switches: scorer.metrics is METRICS plus the switched-on groups' tuples in the table's order.
+    summarise() on a dict of those keys, key number i holding i + 0.5 if it is a _noisy key and i otherwise: the columns come
+    back in that order, and each improvement is enhanced - noisy, or noisy - enhanced for llr, cd and wss.  With these values
+    the right answer for a measure at column i is -1.5 (+1.5 where lower is better); the operands swapped give the other sign,
+    and any other column in either place an amount that is not 1.5."""
+    import itertools
+    from dcsnet.enhance import Enhancer
+    from dcsnet.evaluate import MEASURE_GROUPS, RecordingScorer, summarise
+    switches = ('extended', 'frame_measures', 'spectral_measures', 'sdr')
+    tuples = (RecordingScorer.EXTENDED, RecordingScorer.FRAME_MEASURES, RecordingScorer.SPECTRAL_MEASURES, RecordingScorer.SDR)
+    assert tuple(g.switch for g in MEASURE_GROUPS) == (None,) + switches
+    assert tuple(g.keys for g in MEASURE_GROUPS) == (RecordingScorer.METRICS,) + tuples
+    lower = {k for g in MEASURE_GROUPS for k in g.lower_is_better}
+    assert lower == {'llr', 'cd', 'wss'}
+    for setting in itertools.product((False, True), repeat=4):
+        scorer = RecordingScorer(Enhancer.__new__(Enhancer), extended=setting[0])
+        for name, on in zip(switches[1:], setting[1:]):
+            setattr(scorer, name, on)
+        keys = RecordingScorer.METRICS + sum((t for t, on in zip(tuples, setting) if on), ())
+        assert scorer.metrics == keys, setting
+        scores = {k: torch.full((3,), i + 0.5 * k.endswith('_noisy')) for i, k in enumerate(keys)}
+        summary, table = summarise(dict(reversed(list(scores.items()))))              # the dict's own order does not count
+        assert table.shape == (3, len(keys)) and all((table[:, i] == scores[k].numpy()).all() for i, k in enumerate(keys))
+        measures = [k for k in keys if not k.endswith('_noisy')]
+        assert list(summary) == ['files'] + [k + s for k in keys for s in ('', '_nan')] + [k + '_improvement' for k in measures]
+        for k in measures:
+            assert summary[k + '_improvement'] == (1.5 if k in lower else -1.5), (setting, k)

@@ -9,13 +9,9 @@ an SDR below 80 dB, so no value hinges on last bits.
 
 The largest observed differences go to sdr_parity.json in $DCS_PARITY_DIR (default parity_out/, kept out of git); a full run's
 file is committed as profiles/sdr_parity.json."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
-from scipy.signal import lfilter
 
 from dcsnet import _lib
 from dcsnet import metrics
@@ -24,8 +20,8 @@ from dcsnet import ops
 pytestmark = pytest.mark.gpu
 
 from oracle.seeded_state import fill_state   # noqa: E402
+from _ragged_helpers import ar_noise, ar_pair, flat, record   # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C = ops.SDR_CHUNK
 LENGTHS = (0, 1, 513, 600, C - 1, C, C + 1, 16000, 23457, 48007, 5000)     # 1: the exact +inf pair; 23457: a 2000-sample zero
 SNRS = (0, 10, 20)                                                          # head; the last one: a 3-tap colouring
@@ -39,34 +35,12 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _record(path, value):
-    """Figures -> $DCS_PARITY_DIR/sdr_parity.json (default parity_out/ in the repository): path = nested keys."""
-    out = os.path.join(os.environ.get('DCS_PARITY_DIR') or os.path.join(ROOT, 'parity_out'), 'sdr_parity.json')
-    try:
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        d = json.load(open(out)) if os.path.exists(out) else {}
-        node = d
-        for k in path[:-1]:
-            node = node.setdefault(k, {})
-        node[path[-1]] = value
-        json.dump(d, open(out, 'w'), indent=1, sort_keys=True)
-    except OSError:
-        pass
-
-
 # ---- signals -------------------------------------------------------------------------------------------------------------------
 
-def _pair(L, snr_db, rng, zero_head=0, colouring=None):
-    """float32: AR(2)-shaped noise as the clean signal (through `colouring` on the estimate's side), white noise added at
-    snr_db; zero_head samples of both are exactly 0."""
-    x = lfilter([1.0], [1.0, -1.6, 0.8], rng.standard_normal(L + 200))[200:]
-    v = rng.standard_normal(L)
-    if L:
-        v *= np.linalg.norm(x) / max(np.linalg.norm(v), 1e-30) * 10 ** (-snr_db / 20)
-    xh = x if colouring is None else np.convolve(x, colouring)[:L]
-    x, y = (0.1 * x).astype(np.float32), (0.1 * (xh + v)).astype(np.float32)
-    x[:zero_head], y[:zero_head] = 0.0, 0.0
-    return x, y
+def _coloured_pair(L, snr_db, rng, colouring):
+    """ar_pair with the clean signal passed through the taps `colouring` on the estimate's side."""
+    x, v = ar_noise(L, snr_db, rng)
+    return (0.1 * x).astype(np.float32), (0.1 * (np.convolve(x, colouring)[:L] + v)).astype(np.float32)
 
 
 def _host(x, y, K):
@@ -85,8 +59,10 @@ def _make_set(seed):
     for i, L in enumerate(LENGTHS):
         if L == 1:
             x, y = np.array([0.5], np.float32), np.array([0.25], np.float32)
+        elif L == 5000:
+            x, y = _coloured_pair(L, SNRS[i % 3], rng, [1.0, -0.6, 0.3])
         else:
-            x, y = _pair(L, SNRS[i % 3], rng, zero_head=2000 if L == 23457 else 0, colouring=[1.0, -0.6, 0.3] if L == 5000 else None)
+            x, y = ar_pair(L, SNRS[i % 3], rng, zero_head=2000 if L == 23457 else 0)
         clean.append(x)
         est.append(y)
     return clean, est
@@ -99,17 +75,10 @@ def the_set():
     return clean, est, host
 
 
-def _flat(recs, dev):
-    off = np.zeros(len(recs) + 1, dtype=np.int64)
-    np.cumsum([len(r) for r in recs], out=off[1:])
-    flat = np.concatenate(recs) if off[-1] else np.zeros(0, np.float32)
-    return torch.from_numpy(flat.astype(np.float32)).to(dev), torch.from_numpy(off).to(dev)
-
-
 def _score(clean, est, dev, K=512, est2=None):
-    c, off = _flat(clean, dev)
-    e, _ = _flat(est, dev)
-    return metrics.sdr_ragged(c, e, off, K, estimate2=None if est2 is None else _flat(est2, dev)[0])
+    c, off = flat(clean, dev)
+    e, _ = flat(est, dev)
+    return metrics.sdr_ragged(c, e, off, K, estimate2=None if est2 is None else flat(est2, dev)[0])
 
 
 def _bits(t):
@@ -129,7 +98,7 @@ def _check_against_host(got, host, what):
     worst = float(diff.max()) if ok.any() else 0.0
     ratio = float((diff / tol).max()) if ok.any() else 0.0
     print(f'[sdr] {what}: max |device - host| = {worst:.3e} dB, {ratio:.3f} of the tolerance')
-    _record((what,), {'max_abs_diff': worst, 'max_share_of_tolerance': ratio})
+    record('sdr_parity.json', (what,), {'max_abs_diff': worst, 'max_share_of_tolerance': ratio})
     assert (diff <= tol).all(), (what, g, h)
 
 
@@ -188,8 +157,8 @@ def test_graph_capture(dev, the_set):
     results bit for bit."""
     clean, est, _ = the_set
     clean2, est2 = _make_set(53)
-    c, off = _flat(clean, dev)
-    e, _ = _flat(est, dev)
+    c, off = flat(clean, dev)
+    e, _ = flat(est, dev)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
@@ -199,8 +168,8 @@ def test_graph_capture(dev, the_set):
     with torch.cuda.graph(g):
         one = metrics.sdr_ragged(c, e, off)
         pair = metrics.sdr_ragged(c, e, off, 16, estimate2=c)
-    c2, _ = _flat(clean2, dev)
-    e2, _ = _flat(est2, dev)
+    c2, _ = flat(clean2, dev)
+    e2, _ = flat(est2, dev)
     c.copy_(c2)
     e.copy_(e2)
     eager_one = metrics.sdr_ragged(c2, e2, off)
@@ -225,7 +194,7 @@ GUARD_F, GUARD_B = 12345.0, 0xA5
 ])
 def test_bad_offsets_stay_inside_the_buffers(dev, offsets):
     total = 20000
-    x, y = _pair(total, 10, np.random.default_rng(54))
+    x, y = ar_pair(total, 10, np.random.default_rng(54))
     c, e = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
     off = torch.tensor(offsets, dtype=torch.int64, device=dev)
     n = len(offsets) - 1
@@ -291,7 +260,7 @@ def test_scorer_with_sdr(dev):
     net = fill_state(C_NETWORK(config, hp, 3), 3).to(dev).eval()
     enh = Enhancer(net, mode='dcs', segment_frames=T, overlap_frames=O, batch_segments=S, use_graph=False)
     rng = np.random.default_rng(41)
-    clean, noisy = zip(*(_pair(L, snr, rng) for L, snr in zip(SCORER_LENGTHS, (5, 0, 10, 15))))
+    clean, noisy = zip(*(ar_pair(L, snr, rng) for L, snr in zip(SCORER_LENGTHS, (5, 0, 10, 15))))
     clean, noisy = list(clean), list(noisy)
 
     plain_scorer = RecordingScorer(enh)

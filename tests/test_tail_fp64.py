@@ -11,9 +11,8 @@ allowance (tl.adam_dp_floor: powf's 16 ulp on beta2^t and the rounding of p), an
 rule against the seeded faults.  Every figure goes to $DCS_PARITY_DIR/tail_parity.json (default parity_out/, kept out of git);
 a full run's file is committed as profiles/tail_parity.json.
 """
-import json
+import functools
 import math
-import os
 
 import pytest
 import torch
@@ -21,6 +20,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import tail_fp64 as tl            # noqa: E402
+from _ragged_helpers import record            # noqa: E402
 
 F_BINS = 256
 SCALE = 512 ** 0.5                              # torch.istft(normalized=True) at n_fft = 512
@@ -37,19 +37,7 @@ def dev():
     torch.set_num_threads(old)
 
 
-def _record(path, value):
-    out = os.path.join(os.environ.get('DCS_PARITY_DIR') or
-                       os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'parity_out'), 'tail_parity.json')
-    try:
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        d = json.load(open(out)) if os.path.exists(out) else {}
-        node = d
-        for k in path[:-1]:
-            node = node.setdefault(k, {})
-        node[path[-1]] = value
-        json.dump(d, open(out, 'w'), indent=1, sort_keys=True)
-    except OSError:
-        pass
+_record = functools.partial(record, 'tail_parity.json')     # figures -> $DCS_PARITY_DIR/tail_parity.json (default parity_out/)
 
 
 def _judge(path, got, ref, yard, **kw):

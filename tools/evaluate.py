@@ -124,7 +124,7 @@ def main():
         a.frame_measures = a.spectral_measures = True
     import torch
     from dcsnet.config import config
-    from dcsnet.evaluate import RecordingScorer, summarise
+    from dcsnet.evaluate import MEASURE_GROUPS, RecordingScorer, summarise
     if real:
         from dcsnet.r_network import R_NETWORK as Net
         from dcsnet.enhance import MagnitudeEnhancer as Enh
@@ -138,10 +138,9 @@ def main():
         net.set_activation_dtype('bf16')
     enh = Enh(net, mode=a.mode, segment_frames=a.segment_frames, overlap_frames=a.overlap_frames,
               batch_segments=a.batch_segments, use_graph=not a.no_graph)
-    scorer = RecordingScorer(enh, extended=a.extended)
-    scorer.frame_measures = a.frame_measures
-    scorer.spectral_measures = a.spectral_measures
-    scorer.sdr = a.sdr
+    scorer = RecordingScorer(enh)
+    for g in MEASURE_GROUPS[1:]:                             # --frame-measures -> scorer.frame_measures, and so on
+        setattr(scorer, g.switch, getattr(a, g.switch))
     summary, table = summarise(scorer.score_files(noisy, clean))
     keys = scorer.metrics
     if pesq is not None:

@@ -37,6 +37,7 @@ import os
 import re
 import sys
 import time
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -89,94 +90,59 @@ def pass_stats(times, n):
             'ms_per_pass_min': round(min(times) * 1e3, 3), 'recordings_per_s': round(n / med, 1)}
 
 
-def frame_measures_bench(a, c, e, off, off_h, longest, fs):
-    """The device pass of the three frame measures beside the STOI pass, and the host function on the same set."""
-    n = a.recordings
-    spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
-    methods = (('stoi_ragged_call', lambda: metrics.stoi_ragged(c, e, off, fs, longest=longest)),
-               ('frame_measures_ragged_call', lambda: metrics.frame_measures_ragged(c, e, off, fs, longest=longest)))
-    first = {}
-    for name, fn in methods:
-        first[name] = fn()
-        torch.cuda.synchronize()
-    times = timed_rounds(methods, a.min_seconds)
-    ch, eh = c.cpu().numpy(), e.cpu().numpy()
-    t0 = time.perf_counter()
-    host = [metrics.frame_measures(ch[p:q], eh[p:q], fs) for p, q in spans]
-    host_s = time.perf_counter() - t0
+FP64_VECTOR_PEAK = 78.6e12      # FLOP/s: half the FP32 vector peak of MI355X_MICROARCH (157.3 TFLOPS), AMD's published fp64 figure
+
+
+class Mode(NamedTuple):
+    """What --frame-measures, --spectral-measures or --sdr times beside the STOI pass and holds against the host.  name: the flag's
+    attribute; the metric is '<name>_recordings', the mode's own device pass '<name>_ragged_call'.  out: the default output file
+    under profiles/.  host: (x, y, fs) -> {key: float} of one recording.  keys: what is compared with the host.  methods:
+    (c, e, off, fs, longest) -> ((pass name, function), ...), timed behind the STOI pass in this order.  launches: kernels per pass
+    of those.  fields: (n, total, spans, fs) -> the mode's geometry and workspace.  notes: its note strings.  more: (res, first,
+    a, total) -> the fields only this mode has, from the result so far and the warm-up's values."""
+    name: str
+    out: str
+    host: Callable
+    keys: tuple
+    methods: Callable
+    launches: dict
+    fields: Callable
+    notes: dict = {}
+    more: Callable = lambda res, first, a, total: {}
+
+
+def _frames(spans, fs):
+    return int(sum(metrics.frame_count(q - p, fs) for p, q in spans))
+
+
+def _frame_fields(n, total, spans, fs):
     N, S, P = metrics.frame_geometry(fs)
-    res = {'metric': 'frame_measures_recordings', 'device': torch.cuda.get_device_name(0), 'recordings': n,
-           'audio_seconds': round(float(off_h[-1]) / fs, 2), 'lengths_s': '1 .. 10 s at 16 kHz, uniform, seeded',
-           'frames': int(sum(metrics.frame_count(q - p, fs) for p, q in spans)), 'frame': {'N': N, 'S': S, 'lpc_order': P},
-           'first_measurement': 'no earlier figure exists for this pass on the MI355X and nothing at the parent commit compares',
-           'timing': 'device events around one pass over the set; the two device methods alternate in 3 rounds, each filling a '
-                     'third of min_seconds with repeated passes; median over the passes.  host: wall clock of one loop of '
-                     'metrics.frame_measures over the set (numpy, fp64), signals already on the host',
-           'min_seconds': a.min_seconds,
-           'kernel_launches': {'frame_measures_ragged_call': 3, 'stoi_ragged_call': 2 * 2 + 4, 'stoi_ragged_call_fills': 2},
-           'workspace_bytes': int(ops.frame_measures_workspace_bytes(n, int(off_h[-1]), fs)),
-           'host_loop_s': round(host_s, 4)}
-    for name, _ in methods:
-        res[name] = pass_stats(times[name], n)
-    res['frame_measures_over_stoi_pass'] = round(res['frame_measures_ragged_call']['ms_per_pass_median'] /
-                                                 res['stoi_ragged_call']['ms_per_pass_median'], 3)
-    res['host_loop_over_device_pass'] = round(host_s * 1e3 / res['frame_measures_ragged_call']['ms_per_pass_median'], 1)
-    for k in ('ssnr', 'llr', 'cd'):
-        res[f'{k}_max_abs_diff_vs_host'] = float(np.nanmax(np.abs(first['frame_measures_ragged_call'][k].cpu().numpy() -
-                                                                  np.array([m[k] for m in host]))))
-    return res
+    return {'frames': _frames(spans, fs), 'frame': {'N': N, 'S': S, 'lpc_order': P},
+            'workspace_bytes': int(ops.frame_measures_workspace_bytes(n, total, fs))}
 
 
-def spectral_measures_bench(a, c, e, off, off_h, longest, fs):
-    """The device pass of WSS and fwSegSNR beside the STOI pass and the frame-measures pass, and the host function on the same
-    set."""
-    n = a.recordings
-    spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
-    methods = (('stoi_ragged_call', lambda: metrics.stoi_ragged(c, e, off, fs, longest=longest)),
-               ('frame_measures_ragged_call', lambda: metrics.frame_measures_ragged(c, e, off, fs, longest=longest)),
-               ('spectral_measures_ragged_call', lambda: metrics.spectral_measures_ragged(c, e, off, fs, longest=longest)))
-    first = {}
-    for name, fn in methods:
-        first[name] = fn()
-        torch.cuda.synchronize()
-    times = timed_rounds(methods, a.min_seconds)
-    ch, eh = c.cpu().numpy(), e.cpu().numpy()
-    t0 = time.perf_counter()
-    host = [metrics.spectral_measures(ch[p:q], eh[p:q], fs) for p, q in spans]
-    host_s = time.perf_counter() - t0
+def _spectral_fields(n, total, spans, fs):
     N, S, _ = metrics.frame_geometry(fs)
     nfft = metrics.spectral_fft_size(fs)
-    res = {'metric': 'spectral_measures_recordings', 'device': torch.cuda.get_device_name(0), 'recordings': n,
-           'audio_seconds': round(float(off_h[-1]) / fs, 2), 'lengths_s': '1 .. 10 s at 16 kHz, uniform, seeded',
-           'frames': int(sum(metrics.frame_count(q - p, fs) for p, q in spans)), 'frame': {'N': N, 'S': S, 'nfft': nfft},
-           'first_measurement': 'no earlier figure exists for this pass on the MI355X and nothing at the parent commit compares',
-           'timing': 'device events around one pass over the set; the three device methods alternate in 3 rounds, each filling a '
-                     'third of min_seconds with repeated passes; median over the passes.  host: wall clock of one loop of '
-                     'metrics.spectral_measures over the set (numpy, fp64), signals already on the host',
-           'min_seconds': a.min_seconds,
-           'kernel_launches': {'spectral_measures_ragged_call': 3, 'frame_measures_ragged_call': 3, 'stoi_ragged_call': 2 * 2 + 4,
-                               'stoi_ragged_call_fills': 2},
-           'workspace_bytes': int(ops.spectral_measures_workspace_bytes(n, int(off_h[-1]), fs)),
-           'frame_kernel_lds_bytes_derived': 16 * nfft, 'host_loop_s': round(host_s, 4),
-           'derived': 'frame_kernel_lds_bytes_derived is 16 nfft, what the launch passes as dynamic LDS (the kernel has no static '
-                      'LDS), not a reading of the code object',
-           'differences': 'this set (harmonic signals) does not meet the input condition of '
-                          'tests/test_spectral_measures_device.py (every band slope above 1e-6 dB), and its WSS values are two '
-                          'orders larger than that test\'s: the differences below are float32 roundings of those values and '
-                          'are not to be read against profiles/spectral_measures_parity.json'}
-    for name, _ in methods:
-        res[name] = pass_stats(times[name], n)
-    ms = res['spectral_measures_ragged_call']['ms_per_pass_median']
-    res['spectral_measures_over_stoi_pass'] = round(ms / res['stoi_ragged_call']['ms_per_pass_median'], 3)
-    res['spectral_measures_over_frame_measures_pass'] = round(ms / res['frame_measures_ragged_call']['ms_per_pass_median'], 3)
-    res['host_loop_over_device_pass'] = round(host_s * 1e3 / ms, 1)
-    for k in ('wss', 'fwssnr'):
-        res[f'{k}_max_abs_diff_vs_host'] = float(np.nanmax(np.abs(first['spectral_measures_ragged_call'][k].cpu().numpy() -
-                                                                  np.array([m[k] for m in host]))))
-    return res
+    return {'frames': _frames(spans, fs), 'frame': {'N': N, 'S': S, 'nfft': nfft},
+            'workspace_bytes': int(ops.spectral_measures_workspace_bytes(n, total, fs)), 'frame_kernel_lds_bytes_derived': 16 * nfft}
 
 
-FP64_VECTOR_PEAK = 78.6e12      # FLOP/s: half the FP32 vector peak of MI355X_MICROARCH (157.3 TFLOPS), AMD's published fp64 figure
+def _spectral_more(res, first, a, total):
+    return {'spectral_measures_over_frame_measures_pass': round(res['spectral_measures_ragged_call']['ms_per_pass_median'] /
+                                                                res['frame_measures_ragged_call']['ms_per_pass_median'], 3)}
+
+
+def _sdr_methods(c, e, off, fs, longest):
+    e2 = (c + 0.5 * (e - c)).contiguous()                     # a second estimate: the same noise 6 dB down
+    return (('sdr_ragged_call', lambda: metrics.sdr_ragged(c, e, off)),
+            ('sdr_ragged_two_estimates_call', lambda: metrics.sdr_ragged(c, e, off, estimate2=e2)))
+
+
+def _sdr_fields(n, total, spans, fs):
+    K = metrics.SDR_FILTER_LENGTH
+    return {'filter_length': K, 'chunk': ops.SDR_CHUNK, 'chunks': int(sum(-(-(q - p + K - 1) // ops.SDR_CHUNK) for p, q in spans)),
+            'workspace_bytes': int(ops.sdr_workspace_bytes(n, total, K))}
 
 
 def sdr_kernel_times(path):
@@ -194,15 +160,63 @@ def sdr_kernel_times(path):
     return out
 
 
-def sdr_bench(a, c, e, off, off_h, longest, fs):
-    """The device pass of the BSS-eval SDR with one and with two estimates beside the STOI pass, and the host function on the
-    same set."""
-    n, K = a.recordings, metrics.SDR_FILTER_LENGTH
+def _sdr_more(res, first, a, total):
+    K = metrics.SDR_FILTER_LENGTH
+    one, two = res['sdr_ragged_call']['ms_per_pass_median'], res['sdr_ragged_two_estimates_call']['ms_per_pass_median']
+    # operations from the shapes: the issue's count of the algorithm (5 K L multiply-adds per recording and estimate), and the
+    # multiply-adds the direct form here performs (R, D and the projection: 3 K L; 5 K L with two estimates)
+    out = {'two_estimates_over_two_calls': round(two / (2 * one), 3),
+           'flops': {'algorithmic_fp64_flop_one_estimate': 2 * 5 * K * total, 'direct_form_fp64_flop_one_estimate': 2 * 3 * K * total,
+                     'direct_form_fp64_flop_two_estimates': 2 * 5 * K * total, 'fp64_vector_peak_flops': FP64_VECTOR_PEAK,
+                     'peak_source': 'half the FP32 vector peak of the MI355X guide (157.3 TFLOPS); the guide lists no fp64 figure',
+                     'algorithmic_share_of_peak_whole_pass': round(2 * 5 * K * total / (one * 1e-3) / FP64_VECTOR_PEAK, 4),
+                     'direct_form_share_of_peak_whole_pass': round(2 * 3 * K * total / (one * 1e-3) / FP64_VECTOR_PEAK, 4),
+                     'direct_form_share_of_peak_whole_pass_two_estimates':
+                         round(2 * 5 * K * total / (two * 1e-3) / FP64_VECTOR_PEAK, 4),
+                     'note': 'whole-pass rates over peak (launch gaps and the serial solve included), not a kernel\'s share of peak'},
+           'second_estimate_equals_its_own_call': bool(torch.equal(first['sdr_ragged_two_estimates_call'][0], first['sdr_ragged_call']))}
+    if a.kernel_stats:
+        out['kernel_us_rocprofv3'] = sdr_kernel_times(a.kernel_stats)
+        for tag, k in out['kernel_us_rocprofv3'].items():
+            if len(k) == 4:
+                out[f'solve_share_of_kernel_time_{tag}'] = round(k['solve'] / sum(k.values()), 3)
+    return out
+
+
+def _frame_pass(c, e, off, fs, longest):
+    return ('frame_measures_ragged_call', lambda: metrics.frame_measures_ragged(c, e, off, fs, longest=longest))
+
+
+def _spectral_methods(c, e, off, fs, longest):
+    return (_frame_pass(c, e, off, fs, longest),
+            ('spectral_measures_ragged_call', lambda: metrics.spectral_measures_ragged(c, e, off, fs, longest=longest)))
+
+
+MODES = (
+    Mode(name='frame_measures', out='frame_measures_bench.json', host=metrics.frame_measures, keys=('ssnr', 'llr', 'cd'),
+         methods=lambda *buffers: (_frame_pass(*buffers),), launches={'frame_measures_ragged_call': 3}, fields=_frame_fields),
+    Mode(name='spectral_measures', out='spectral_measures_bench.json', host=metrics.spectral_measures, keys=('wss', 'fwssnr'),
+         methods=_spectral_methods, launches={'spectral_measures_ragged_call': 3, 'frame_measures_ragged_call': 3},
+         fields=_spectral_fields, more=_spectral_more,
+         notes={'derived': 'frame_kernel_lds_bytes_derived is 16 nfft, what the launch passes as dynamic LDS (the kernel has no '
+                           'static LDS), not a reading of the code object',
+                'differences': 'this set (harmonic signals) does not meet the input condition of '
+                               'tests/test_spectral_measures_device.py (every band slope above 1e-6 dB), and its WSS values are two '
+                               'orders larger than that test\'s: the differences below are float32 roundings of those values and '
+                               'are not to be read against profiles/spectral_measures_parity.json'}),
+    Mode(name='sdr', out='sdr_bench.json', host=lambda x, y, fs: {'sdr': metrics.sdr(x, y)}, keys=('sdr',), methods=_sdr_methods,
+         launches={'sdr_ragged_call': ops.SDR_LAUNCHES, 'sdr_ragged_two_estimates_call': ops.SDR_LAUNCHES},
+         fields=_sdr_fields, more=_sdr_more,
+         notes={'differences': 'this set (harmonic signals, a broadband part 30 dB down) is far worse conditioned than the set of '
+                               'tests/test_sdr_device.py; the difference above is not to be read against profiles/sdr_parity.json'}),
+)
+
+
+def measure_bench(mode, a, c, e, off, off_h, longest, fs):
+    """The device passes of one mode beside the STOI pass, and its host function on the same set."""
+    n, total, own = a.recordings, int(off_h[-1]), f'{mode.name}_ragged_call'
     spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
-    e2 = (c + 0.5 * (e - c)).contiguous()                     # a second estimate: the same noise 6 dB down
-    methods = (('stoi_ragged_call', lambda: metrics.stoi_ragged(c, e, off, fs, longest=longest)),
-               ('sdr_ragged_call', lambda: metrics.sdr_ragged(c, e, off)),
-               ('sdr_ragged_two_estimates_call', lambda: metrics.sdr_ragged(c, e, off, estimate2=e2)))
+    methods = (('stoi_ragged_call', lambda: metrics.stoi_ragged(c, e, off, fs, longest=longest)),) + mode.methods(c, e, off, fs, longest)
     first = {}
     for name, fn in methods:
         first[name] = fn()
@@ -210,46 +224,26 @@ def sdr_bench(a, c, e, off, off_h, longest, fs):
     times = timed_rounds(methods, a.min_seconds)
     ch, eh = c.cpu().numpy(), e.cpu().numpy()
     t0 = time.perf_counter()
-    host = np.array([metrics.sdr(ch[p:q], eh[p:q]) for p, q in spans])
+    host = [mode.host(ch[p:q], eh[p:q], fs) for p, q in spans]
     host_s = time.perf_counter() - t0
-    total = int(off_h[-1])
-    res = {'metric': 'sdr_recordings', 'device': torch.cuda.get_device_name(0), 'recordings': n,
-           'audio_seconds': round(total / fs, 2), 'lengths_s': '1 .. 10 s at 16 kHz, uniform, seeded', 'filter_length': K,
-           'chunk': ops.SDR_CHUNK, 'chunks': int(sum(-(-(q - p + K - 1) // ops.SDR_CHUNK) for p, q in spans)),
+    res = {'metric': f'{mode.name}_recordings', 'device': torch.cuda.get_device_name(0), 'recordings': n,
+           'audio_seconds': round(total / fs, 2), 'lengths_s': '1 .. 10 s at 16 kHz, uniform, seeded',
            'first_measurement': 'no earlier figure exists for this pass on the MI355X and nothing at the parent commit compares',
-           'timing': 'device events around one pass over the set; the three device methods alternate in 3 rounds, each filling a '
-                     'third of min_seconds with repeated passes; median over the passes.  host: wall clock of one loop of '
-                     'metrics.sdr over the set (numpy, fp64), signals already on the host',
+           'timing': f'device events around one pass over the set; the {("two", "three")[len(methods) - 2]} device methods alternate '
+                     'in 3 rounds, each filling a third of min_seconds with repeated passes; median over the passes.  host: wall '
+                     f'clock of one loop of metrics.{mode.name} over the set (numpy, fp64), signals already on the host',
            'min_seconds': a.min_seconds,
-           'kernel_launches': {'sdr_ragged_call': ops.SDR_LAUNCHES, 'sdr_ragged_two_estimates_call': ops.SDR_LAUNCHES,
-                               'stoi_ragged_call': 2 * 2 + 4, 'stoi_ragged_call_fills': 2},
-           'workspace_bytes': int(ops.sdr_workspace_bytes(n, total, K)), 'host_loop_s': round(host_s, 4)}
+           'kernel_launches': dict(mode.launches, stoi_ragged_call=2 * 2 + 4, stoi_ragged_call_fills=2),
+           **mode.fields(n, total, spans, fs), 'host_loop_s': round(host_s, 4), **mode.notes}
     for name, _ in methods:
         res[name] = pass_stats(times[name], n)
-    one, two = res['sdr_ragged_call']['ms_per_pass_median'], res['sdr_ragged_two_estimates_call']['ms_per_pass_median']
-    res['sdr_over_stoi_pass'] = round(one / res['stoi_ragged_call']['ms_per_pass_median'], 3)
-    res['two_estimates_over_two_calls'] = round(two / (2 * one), 3)
-    res['host_loop_over_device_pass'] = round(host_s * 1e3 / one, 1)
-    # operations from the shapes: the issue's count of the algorithm (5 K L multiply-adds per recording and estimate), and the
-    # multiply-adds the direct form here performs (R, D and the projection: 3 K L; 5 K L with two estimates)
-    res['flops'] = {'algorithmic_fp64_flop_one_estimate': 2 * 5 * K * total, 'direct_form_fp64_flop_one_estimate': 2 * 3 * K * total,
-                    'direct_form_fp64_flop_two_estimates': 2 * 5 * K * total, 'fp64_vector_peak_flops': FP64_VECTOR_PEAK,
-                    'peak_source': 'half the FP32 vector peak of the MI355X guide (157.3 TFLOPS); the guide lists no fp64 figure',
-                    'algorithmic_share_of_peak_whole_pass': round(2 * 5 * K * total / (one * 1e-3) / FP64_VECTOR_PEAK, 4),
-                    'direct_form_share_of_peak_whole_pass': round(2 * 3 * K * total / (one * 1e-3) / FP64_VECTOR_PEAK, 4),
-                    'direct_form_share_of_peak_whole_pass_two_estimates':
-                        round(2 * 5 * K * total / (two * 1e-3) / FP64_VECTOR_PEAK, 4),
-                    'note': 'whole-pass rates over peak (launch gaps and the serial solve included), not a kernel\'s share of peak'}
-    got = first['sdr_ragged_call'].cpu().numpy().astype(np.float64)
-    res['sdr_max_abs_diff_vs_host'] = float(np.nanmax(np.abs(got - host)))
-    res['second_estimate_equals_its_own_call'] = bool(torch.equal(first['sdr_ragged_two_estimates_call'][0], first['sdr_ragged_call']))
-    res['differences'] = ('this set (harmonic signals, a broadband part 30 dB down) is far worse conditioned than the set of '
-                          'tests/test_sdr_device.py; the difference above is not to be read against profiles/sdr_parity.json')
-    if a.kernel_stats:
-        res['kernel_us_rocprofv3'] = sdr_kernel_times(a.kernel_stats)
-        for tag, k in res['kernel_us_rocprofv3'].items():
-            if len(k) == 4:
-                res[f'solve_share_of_kernel_time_{tag}'] = round(k['solve'] / sum(k.values()), 3)
+    ms = res[own]['ms_per_pass_median']
+    res[f'{mode.name}_over_stoi_pass'] = round(ms / res['stoi_ragged_call']['ms_per_pass_median'], 3)
+    res['host_loop_over_device_pass'] = round(host_s * 1e3 / ms, 1)
+    got = first[own] if isinstance(first[own], dict) else {mode.keys[0]: first[own]}
+    for k in mode.keys:
+        res[f'{k}_max_abs_diff_vs_host'] = float(np.nanmax(np.abs(got[k].cpu().numpy() - np.array([m[k] for m in host]))))
+    res.update(mode.more(res, first, a, total))
     return res
 
 
@@ -272,10 +266,9 @@ def main():
     ap.add_argument('--extended', action='store_true', help="time stoi_ragged(extended='both') beside the STOI-only call")
     ap.add_argument('--parent-json', default=None, help="this tool's JSON of the parent commit, same box, same session")
     a = ap.parse_args()
+    mode = next((m for m in reversed(MODES) if getattr(a, m.name)), None)       # of several flags, the last of MODES
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'sdr_bench.json' if a.sdr else
-                             'spectral_measures_bench.json' if a.spectral_measures else
-                             'frame_measures_bench.json' if a.frame_measures else 'score_bench.json')
+        a.out = os.path.join(ROOT, 'profiles', mode.out if mode else 'score_bench.json')
     dev = torch.device('cuda:0')
     fs = 16000
     clean, est = synthetic_set(a.recordings, a.seed, fs)
@@ -286,12 +279,8 @@ def main():
     off = torch.from_numpy(off_h).to(dev)
     longest = int(np.diff(off_h).max())
     spans = list(zip(off_h[:-1].tolist(), off_h[1:].tolist()))
-    if a.sdr:
-        return write_result(sdr_bench(a, c, e, off, off_h, longest, fs), a.out)
-    if a.spectral_measures:
-        return write_result(spectral_measures_bench(a, c, e, off, off_h, longest, fs), a.out)
-    if a.frame_measures:
-        return write_result(frame_measures_bench(a, c, e, off, off_h, longest, fs), a.out)
+    if mode:
+        return write_result(measure_bench(mode, a, c, e, off, off_h, longest, fs), a.out)
 
     def ragged():
         return metrics.stoi_ragged(c, e, off, fs, longest=longest)
