@@ -538,25 +538,18 @@ class TrainStep:
             side = self.__dict__.get('_wgrad_side')
             if side is None or side.device != loss.device:
                 side = self.__dict__['_wgrad_side'] = torch.cuda.Stream(device=loss.device)
-        ops.wgrad_defer_begin()
+        scope = ops.wgrad_defer_begin(side)
         functional._POOL_ADD.clear()                                   # (left over if an earlier backward raised mid-pass: ADVICE r4)
-        del functional.PENDING_SIDE[:]
-        functional.WGRAD_SIDE = side
-        functional.FLUSH_AT_NEXT_FORK = False
         try:
             if one is None:
                 loss.backward()
             else:
                 loss.backward(gradient=one)
         finally:
-            functional.WGRAD_SIDE = None
-            if functional.PENDING_SIDE:                            # (queued after the last fork: none in the networks of this repo)
-                if side is not None:
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        functional._run_pending_side()
-                else:
-                    functional._run_pending_side()
+            if scope.pending_side:                                 # (queued after the last fork: none in the networks of this repo)
+                side.wait_stream(torch.cuda.current_stream())      # (jobs are queued only where there is a side stream)
+                with torch.cuda.stream(side):
+                    functional._run_pending_side(scope)
             if side is not None:
                 torch.cuda.current_stream().wait_stream(side)      # the one join: every weight-gradient kernel is in
             ops.wgrad_defer_flush()

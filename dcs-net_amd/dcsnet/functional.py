@@ -85,9 +85,7 @@ def packed_weight(w_r, w_i, b_r, b_i, transposed, up=(1, 1), tap_rows=0):
 
 ATTENTION_BATCH_MAX = ops.ATTENTION_BATCH_MAX
 
-FLUSH_AT_NEXT_FORK = False   # set by the batched skip-attention backward: the next conv fork also flushes the recorded 7x7 problems
-WGRAD_SIDE = None      # the side stream the deferred weight-gradient kernels of a train step run on (dp.TrainStep._backward), else None
-sink_hits = 0          # diagnostics: how many parameter gradients were routed to a sink
+sink_hits = 0         # diagnostics: how many parameter gradients were routed to a sink
 
 
 def _sink(p):
@@ -105,17 +103,21 @@ def _sink(p):
 
 
 DEFER_FC = os.environ.get('DCS_DEFER_FC', '1') != '0'      # 0: the attention blocks' FC weight gradients stay on the main chain (A/B)
-PENDING_SIDE = []          # launches nothing downstream waits for, queued by backward nodes for the next fork of the side stream
 
 
-def _run_pending_side():
-    """Issue the queued launches on the CURRENT stream (the side stream right after a fork, or — dp.TrainStep._backward — whatever
-    is left before the join); their operands stay alive until the join (ops.WGRAD_DEFER)."""
-    while PENDING_SIDE:
-        job = PENDING_SIDE.pop(0)
+def _two_stream_scope():
+    """The open deferred-reduce scope (ops.WgradScope) when the backward pass runs on two streams (dp.TrainStep._backward), else None."""
+    scope = ops.WGRAD_DEFER
+    return scope if scope is not None and scope.side is not None else None
+
+
+def _run_pending_side(scope):
+    """Issue the scope's queued launches on the CURRENT stream (the side stream right after a fork, or — dp.TrainStep._backward —
+    whatever is left before the join); their operands stay alive until the join (scope.keep)."""
+    while scope.pending_side:
+        job = scope.pending_side.pop(0)
         ops.attention_bwd_fc_weights(job)
-        if ops.WGRAD_DEFER is not None:
-            ops.WGRAD_DEFER.append(job)
+        scope.keep.append(job)
 
 
 class _CConv2dFn(torch.autograd.Function):
@@ -152,9 +154,10 @@ class _CConv2dFn(torch.autograd.Function):
         # is queued, and joins once, in front of the flush (dp.TrainStep._backward) — it runs beside this layer's data
         # gradient and under the launch-bound CBN / attention backward kernels of the next layer, which leave most CUs idle.
         side = None
-        if (want_w and WGRAD_SIDE is not None and ops.WGRAD_DEFER is not None and gy.is_cuda and
+        scope = _two_stream_scope()
+        if (want_w and scope is not None and gy.is_cuda and
                 ctx.sinks[0] is not None and ctx.sinks[1] is not None and (not has_bias or (ctx.sinks[2] is not None and ctx.sinks[3] is not None))):
-            side = WGRAD_SIDE
+            side = scope.side
             side.wait_stream(torch.cuda.current_stream())
         if need[0] or need[1]:
             C1 = x1.shape[3]
@@ -164,14 +167,13 @@ class _CConv2dFn(torch.autograd.Function):
         if want_w:
             if side is not None:
                 with torch.cuda.stream(side):
-                    _run_pending_side()
+                    _run_pending_side(scope)
                     g = ops.cconv2d_bwd_weight(x1, x2, gy, w_shape, has_bias, ksize, stride, pad, up, transposed, ctx.sinks,
                                                immediate=True)
-                    global FLUSH_AT_NEXT_FORK
-                    if FLUSH_AT_NEXT_FORK:
+                    if scope.flush_at_next_fork:
                         # every 7x7 attention-conv problem of the step is recorded by now (the batched skip attentions came last):
                         # their one batched kernel and its reductions ride on this fork and run beside the LSTM backward
-                        FLUSH_AT_NEXT_FORK = False
+                        scope.flush_at_next_fork = False
                         ops.wgrad_defer_flush(partial=True)
             else:
                 g = ops.cconv2d_bwd_weight(x1, x2, gy, w_shape, has_bias, ksize, stride, pad, up, transposed, ctx.sinks)
@@ -371,11 +373,12 @@ class _CbnAttentionFn(torch.autograd.Function):
         sk = ctx.sinks
         # inside TrainStep's two-stream backward the block's FC weight gradients (a launch nothing downstream waits for) are
         # queued for the side stream: they ride the next conv layer's fork (_run_pending_side)
-        defer = DEFER_FC and WGRAD_SIDE is not None and ops.WGRAD_DEFER is not None and all(s_ is not None for s_ in sk[2:6])
+        scope = _two_stream_scope()
+        defer = DEFER_FC and scope is not None and all(s_ is not None for s_ in sk[2:6])
         g = ops.attention_bwd(a, g_out.contiguous(), ca, sa, sp, pooled, hidden, w1, w2, wsa, ksize, drop_p, seed, sk[2:],
                               split_pool=True, defer_fc=defer)
         if defer:
-            PENDING_SIDE.append(g[8])
+            scope.pending_side.append(g[8])
         g_x, g_w, g_b = ops.cbn_bwd(x, g[0], weight, stats, coef, use_batch, act, 0.0, 0, affine, sk[:2], g_add=g[7])
         full = (g_w, g_b, *g[1:7])
         gp = tuple(None if s_ is not None else t for t, s_ in zip(full, sk))
@@ -451,10 +454,10 @@ class _AttentionBlocksFn(torch.autograd.Function):
             full = (*fcs[i], g_c1r, g_c1i)
             grads_x.append(g_x)
             grads_p += [None if s_ is not None else g_ for g_, s_ in zip(full, sk)]
-        global FLUSH_AT_NEXT_FORK
-        if WGRAD_SIDE is not None and ops.WGRAD_DEFER is not None:
-            ops.WGRAD_DEFER.append((sps, [r[1] for r in res]))
-            FLUSH_AT_NEXT_FORK = True
+        scope = _two_stream_scope()
+        if scope is not None:
+            scope.keep.append((sps, [r[1] for r in res]))
+            scope.flush_at_next_fork = True
         return (None, None, None, *grads_x, *grads_p)
 
 
@@ -670,7 +673,7 @@ class _LstmLayerFn(torch.autograd.Function):
         NT = B2 * S
         g_pre, b_part = ops.lstm_layer_bwd(g_out.contiguous(), gates, c, w_hh, 2, B2, S, True)
         g_gx = g_pre.view(2, NT, 8 * H)
-        # (queued for the side stream like the attention blocks' FC weight gradients — PENDING_SIDE — the two MFMA products and the
+        # (queued for the side stream like the attention blocks' FC weight gradients — WgradScope.pending_side — the two MFMA products and the
         # reduction of a layer, ~40 us, run beside the encoder's backward and the step is 0.012 ms SLOWER: profiles/r04_side_stream_ab.txt)
         _LstmLayerFn._param_grads(st, inp, hprev, g_pre, b_part, g_gx, B2, S, H, NT, planes=ctx.planes)
         if ctx.planes:
@@ -912,7 +915,8 @@ class _Up2SingleFn(torch.autograd.Function):
             # Round 5: both gradients straight from the cotangent (conv_up1.hip: tap sums in registers) — no tap-channel tensor, two
             # kernels + a 5-workgroup reduce instead of six launches.  Train step: the weight / bias gradient goes to the
             # weight-gradient side stream like every other layer's (forked in front of the data gradient, issued behind it)
-            side = WGRAD_SIDE if (want_w and ops.WGRAD_DEFER is not None and g.is_cuda and sk[0] is not None and sk[1] is not None) else None
+            scope = _two_stream_scope()
+            side = scope.side if (want_w and scope is not None and g.is_cuda and sk[0] is not None and sk[1] is not None) else None
             if side is not None:
                 side.wait_stream(torch.cuda.current_stream())
             elif want_w:
@@ -924,7 +928,7 @@ class _Up2SingleFn(torch.autograd.Function):
             if side is not None:
                 with torch.cuda.stream(side):
                     ops.cconv_up2_single_bwd_weight(g, x1, x2, ctx.w_shape, sk[:2], dst)
-                ops.WGRAD_DEFER.append((g, x1, x2))               # alive until the join
+                scope.keep.append((g, x1, x2))                    # alive until the join
             return gx1, gx2, gw_r, gw_i, gb[0], gb[1], None
         # other channel splits: the factored form (tap sums as a tensor, then the 1x1 tap conv's two gradients)
         gz = ops.tapsum((B, Hs, Ws, ctx.ct, 2), (3, 3), (2, 2), (1, 1), backward=True, grad=g, bias_grad=dst,

@@ -432,7 +432,7 @@ def cconv2d_bwd_weight(x1, x2, gy, w_shape, has_bias, ksize, stride, pad, up=(1,
     all_out = outs is not None and o[0] is not None and o[1] is not None and (not has_bias or (o[2] is not None and o[3] is not None))
     if scope is not None and all_out:
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        scope.append((ws, x1, x2, gy))                # a deferred KERNEL (the small-channel one) still reads its inputs at the flush
+        scope.keep.append((ws, x1, x2, gy))           # a deferred KERNEL (the small-channel one) still reads its inputs at the flush
     else:
         ws = _workspace(nbytes, dev)
     # immediate (the side-stream calls of a train step: functional._CConv2dFn.backward): the slab reduce follows its kernel on
@@ -459,14 +459,25 @@ def cconv2d_bwd_weight(x1, x2, gy, w_shape, has_bias, ksize, stride, pad, up=(1,
     return gw_r, gw_i, gb_r, gb_i
 
 
-WGRAD_DEFER = None         # keep-alive list of slab workspaces while a deferred-reduce scope is open, else None
+class WgradScope:
+    """A deferred-reduce scope of one backward pass; a new one starts empty, so there is nothing to reset between passes."""
+
+    def __init__(self, side=None):
+        self.keep = []                     # slab workspaces and operands kept alive until the final flush
+        self.side = side                   # the stream the weight-gradient kernels of a train step run on (dp.TrainStep._backward), or None
+        self.pending_side = []             # launches nothing downstream waits for, queued by backward nodes for the next fork of the side stream
+        self.flush_at_next_fork = False    # set by the batched skip-attention backward: the next conv fork also flushes the recorded 7x7 problems
 
 
-def wgrad_defer_begin():
+WGRAD_DEFER = None         # the open WgradScope, else None
+
+
+def wgrad_defer_begin(side=None):
     """Open a scope in which weight-gradient slab reductions are recorded instead of launched (dcs_wgrad_defer_begin)."""
     global WGRAD_DEFER
     check(_lib.load().dcs_wgrad_defer_begin(), 'dcs_wgrad_defer_begin')
-    WGRAD_DEFER = []
+    WGRAD_DEFER = WgradScope(side)
+    return WGRAD_DEFER
 
 
 def wgrad_defer_flush(partial=False):
@@ -484,7 +495,6 @@ def wgrad_defer_flush(partial=False):
         check(_lib.load().dcs_wgrad_defer_begin(), 'dcs_wgrad_defer_begin')
     if ev is not None:
         CONV_TIMER.end(ev)
-
 
 
 def cbn(x, weight, bias, running_mean, running_covar, eps=1e-5, momentum=0.1, use_batch_stats=True,

@@ -189,8 +189,44 @@ def test_train_step_side_stream_switch_and_cpu_backward(monkeypatch):
     p0 = ts.bucket.params[0]
     ts.bucket.zero_grad()
     ts._backward((p0 * p0).sum())
-    assert functional.WGRAD_SIDE is None and ops.WGRAD_DEFER is None and '_wgrad_side' not in ts.__dict__
+    assert ops.WGRAD_DEFER is None and '_wgrad_side' not in ts.__dict__
+    assert not any(hasattr(functional, n) for n in ('WGRAD_SIDE', 'PENDING_SIDE', 'FLUSH_AT_NEXT_FORK'))
     assert torch.allclose(p0.grad, 2 * p0.detach())
+
+
+def test_train_step_leaves_nothing_on_the_network():
+    """After a TrainStep call the network's __dict__ holds the keys it held before and no deferred-reduce scope is open, whether
+    the step function returned or raised."""
+    from dcsnet import ops
+    from dcsnet.dp import TrainStep, TorchAdam
+    m = _OracleAdapter(seed=2)
+    ts = TrainStep(m, optimizer_cls=TorchAdam)
+    keys = set(m.__dict__)
+    loss = ts(_batch(0), 0)
+    assert loss is not None and float(loss) == float(loss)
+    assert set(m.__dict__) == keys and ops.WGRAD_DEFER is None
+
+    def raising(batch, idx):
+        raise RuntimeError('from the step function')
+
+    m.training_step = raising
+    with pytest.raises(RuntimeError, match='from the step function'):
+        ts(_batch(0), 1)
+    del m.training_step
+    assert set(m.__dict__) == keys and ops.WGRAD_DEFER is None
+
+
+def test_a_new_wgrad_scope_starts_empty():
+    """ops.WgradScope (what wgrad_defer_begin opens; the entry points themselves need the library): nothing of an earlier
+    backward pass can be in a new one."""
+    from dcsnet import ops
+    side = object()
+    for given in (None, side):
+        s = ops.WgradScope(given) if given is not None else ops.WgradScope()
+        assert s.keep == [] and s.pending_side == [] and s.flush_at_next_fork is False and s.side is given
+    a, b = ops.WgradScope(), ops.WgradScope()
+    a.keep.append(1); a.pending_side.append(2)
+    assert b.keep == [] and b.pending_side == []             # (no list shared between scopes)
 
 
 def test_bench_gpus_flag_launches_its_own_ranks_and_refuses_a_mismatch():

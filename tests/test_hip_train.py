@@ -19,6 +19,14 @@ def dev():
     return torch.device('cuda:0')
 
 
+def _assert_no_step_state(net):
+    """Nothing of a step is live on the network: no weight re-layout left for a forward, no NaN flag for a loss assembly, no
+    batch count left to the step, no pending dropout."""
+    d = net.__dict__
+    assert '_dcs_pack_fork' not in d and '_pending_dropout' not in d
+    assert d.get('_dcs_skip_flag') is None and not d.get('_dcs_defer_nbt', False)
+
+
 class _Toy(torch.nn.Module):
     def __init__(self):
         super().__init__()
@@ -260,7 +268,7 @@ def test_weight_relayout_on_its_own_stream_changes_nothing(dev, graph):
             losses = [float(ts(batch)) for _ in range(5)]
         else:                                  # the graph's launches issued eagerly (the first call records the plan)
             losses = [float(ts(batch))] + [float(ts.uncaptured_step(batch)) for _ in range(4)]
-        assert '_dcs_pack_fork' not in net.__dict__
+        _assert_no_step_state(net)
         assert ('_pack_stream' in net.__dict__) == fork
         runs.append((losses, ts))
     (l0, ts0), (l1, ts1) = runs
@@ -475,3 +483,62 @@ def test_side_stream_weight_gradients_are_bit_identical(dev, graph, storage):
     if g0 is not None:
         assert torch.equal(g0, g1)
     assert all(torch.isfinite(torch.tensor(l1)))
+
+
+def test_a_step_that_raises_mid_backward_leaves_no_scope_behind(dev):
+    """A host-side exception in the middle of the backward pass — here from a tensor hook on the LSTM's input, i.e. after the
+    decoder's backward with its side-stream forks and queued FC jobs has run — propagates, and leaves nothing behind (no step
+    state on the network, no ops.WgradScope open): a weight-gradient call outside any scope reduces at once, and the
+    next steps are bit for bit those of a fresh twin (fresh network, fresh TrainStep) loaded with the same state."""
+    from dcsnet import ops
+    from dcsnet.config import config, hparams
+    from dcsnet.c_network import C_NETWORK
+    from dcsnet.dp import TrainStep
+    hp = dict(hparams)
+    hp['dropout_conv'], hp['dropout_fc'] = 0.0, 0.0
+    clean, noise = seeded_input(2, 256, 32, 1, 0.1), seeded_input(2, 256, 32, 2, 0.05)
+    batch = (noise.to(dev), (clean + noise).to(dev), clean.to(dev), [0, 1])
+    # one weight-gradient problem with a slab reduction (a geometry of test_hip_parity), evaluated before any step
+    g = torch.Generator().manual_seed(5)
+    x, gy = torch.randn(2, 8, 32, 128, 2, generator=g).to(dev), torch.randn(2, 8, 32, 128, 2, generator=g).to(dev)
+    wgrad = lambda outs=None: ops.cconv2d_bwd_weight(x, None, gy, (128, 128, 3, 3), True, (3, 3), (1, 1), (1, 1), (1, 1), False, outs)
+    want = [t.clone() for t in wgrad()]
+
+    net = fill_state(C_NETWORK(config, hp, 0), 2).to(dev).train()
+    ts = TrainStep(net, use_graph=False)
+    good = [float(ts(batch)) for _ in range(2)]
+    assert all(v == v for v in good)
+
+    def raiser(grad):
+        raise RuntimeError('from a hook in the middle of backward')
+
+    def hook_the_input(mod, args):
+        args[0].register_hook(raiser)
+
+    handle = net.lstm.register_forward_pre_hook(hook_the_input)
+    try:
+        with pytest.raises(RuntimeError, match='from a hook in the middle of backward'):
+            ts(batch)
+    finally:
+        handle.remove()
+    torch.cuda.synchronize()
+    _assert_no_step_state(net)
+    assert ops.WGRAD_DEFER is None
+    outs = tuple(torch.full_like(t, float('nan')) for t in want)
+    wgrad(outs)                                            # (a reduction left recording would never write these)
+    torch.cuda.synchronize()
+    for a, b in zip(want, outs):
+        assert torch.equal(a, b)
+
+    twin = fill_state(C_NETWORK(config, hp, 0), 3).to(dev).train()
+    twin.load_state_dict(net.state_dict())
+    ts2 = TrainStep(twin, use_graph=False)
+    ts2.load_state_dict(ts.state_dict())
+    for _ in range(2):
+        a, b = float(ts(batch)), float(ts2(batch))
+        assert a == b, (a, b)
+        _assert_no_step_state(net)
+    torch.cuda.synchronize()
+    for a, b in ((ts.bucket.flat, ts2.bucket.flat), (ts.bucket.grad_all, ts2.bucket.grad_all), (ts.opt.m, ts2.opt.m),
+                 (ts.opt.v, ts2.opt.v), (ts.opt.vmax, ts2.opt.vmax)):
+        assert torch.equal(a, b)

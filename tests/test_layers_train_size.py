@@ -469,7 +469,7 @@ def test_weight_gradients_in_one_deferred_scope(dev, B, mode):
             for y, gy, p in reversed(graphs):
                 y.backward(gy)
             # one recorded slab reduction per layer that has one (dec6's own kernel reduces by itself): nothing ran immediately
-            assert len(ops.WGRAD_DEFER) == len(CONV_LAYERS) - 1, len(ops.WGRAD_DEFER)
+            assert len(ops.WGRAD_DEFER.keep) == len(CONV_LAYERS) - 1, len(ops.WGRAD_DEFER.keep)
         finally:
             ops.wgrad_defer_flush()
         torch.cuda.synchronize()
